@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: env-steps/sec of task.step() on synthetic actions.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dynamics|depth]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dynamics|depth] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps (one region), writes the last timed step's outputs when
+--dump-outputs is given and prints the line.  Everything else -- the regions right after reset(), the median of
+several regions, rooflines, CPU baselines, the +depth / LiDAR / strict-RNG legs, the live parity check, the N > 1
+exchange preflight, diagnostics and other backends, bench_detail.json -- runs only with --full.
 
 N = 1 : BASELINE.json configs[1] -- base_quadrotor, position-setpoint task, Lee position
         controller, 8192 envs, empty_env, dynamics only -- plus (extra keys, same JSON line)
@@ -41,7 +46,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps each; `value` is their median")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each; `value` is their median (default: 1, with --full 5)")
     ap.add_argument("--num-envs", type=int, default=None, help="envs per GPU (default: 8192; 4096 for the LiDAR workloads, BASELINE configs[3])")
     ap.add_argument("--workload", default="dynamics", choices=["dynamics", "depth", "lidar", "lidar_velocity", "lidar_nav"])
     ap.add_argument("--no-depth", action="store_true", help="skip the +depth config (BASELINE configs[2]) extra keys")
@@ -50,17 +56,24 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync-gather", action="store_true", help="N > 1: wait for each step's all-gather before the next step")
     ap.add_argument("--exchange", default="auto", choices=["auto", "process_group", "rccl_thread", "peer_push"],
-                    help="N > 1: who enqueues the per-step all-gather. auto = time both (torch's process group first, then the "
-                         "library's RCCL worker thread under a watchdog) and report the faster one as `value`")
+                    help="N > 1: who enqueues the per-step all-gather. auto = torch's process group; with --full, time both (torch's "
+                         "process group first, then the library's RCCL worker thread under a watchdog) and report the faster one as `value`")
     ap.add_argument("--strict-rng", action="store_true", help="reference-faithful RNG consumption (host sync per step)")
     ap.add_argument("--exchange-selftest-only", action="store_true",
                     help="no timing: build every exchange backend (process_group, peer_push, rccl_thread) on the N ranks, run "
                          "--selftest-steps checksum-verified exchange steps on each and print ONE JSON verdict line per backend")
     ap.add_argument("--selftest-steps", type=int, default=1000)
     ap.add_argument("--preflight-steps", type=int, default=200,
-                    help="N > 1: checksum-verified exchange steps per backend BEFORE anything is timed (0 = skip); the verdicts go to "
-                         "stderr and into the line's exchange.preflight")
+                    help="N > 1 with --full: checksum-verified exchange steps per backend BEFORE anything is timed (0 = skip); the "
+                         "verdicts go to stderr and into the line's exchange.preflight")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: synchronised-episode regions, rooflines, CPU baselines, the +depth / "
+                         "LiDAR / strict-RNG legs, live parity, N > 1 preflight / diagnostics / other exchange backends, bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the last timed task.step() returned, as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
     if args.num_envs is None:
         args.num_envs = 4096 if args.workload in ("lidar", "lidar_velocity") else 8192
     return args
@@ -117,12 +130,13 @@ def timed_steps(task, actions, steps, warmup, world, gather_buf=None, overlap=Tr
     env = task.sim_env
 
     def one(i):
-        task.step(actions[i % len(actions)])
+        res = task.step(actions[i % len(actions)])
         if gather_buf is not None:
             # ONE RCCL all-gather per env step of the rows the observation kernel wrote (obs | reward |
             # terminated | truncated of every env of every rank); with `overlap` it stays in flight
             # while the next step computes and the previous step's result is handed out
             gather_buf.exchange(env._parity, overlap=overlap)
+        return res
 
     # set-up has finished on the device before the warm-up starts: the launches that follow a process's FIRST device
     # synchronize are slow (+0.09 ms over the next ~20 steps, profiles/r02_short_run_probe.txt); without this line that first
@@ -135,9 +149,10 @@ def timed_steps(task, actions, steps, warmup, world, gather_buf=None, overlap=Tr
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
-        one(i)
+        last = one(i)
     timed_steps.last_host_s = time.perf_counter() - t0  # the host's share: all launches of the region enqueued (rank-local clock)
     if gather_buf is not None:
         gather_buf.flush()  # the last collective is inside the timed region
@@ -149,6 +164,7 @@ def timed_steps(task, actions, steps, warmup, world, gather_buf=None, overlap=Tr
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    timed_steps.last_result = last  # what the region's last task.step() returned (--dump-outputs)
     return dt
 
 
@@ -862,17 +878,55 @@ def write_detail(out):
     return path
 
 
-def emit_line(out, fd=None):
+def emit_line(out, fd=None, detail=True):
     """the ONE JSON line, on the process's original stdout: the compact form (< LINE_LIMIT bytes); the full record goes to
-    bench_detail.json"""
+    bench_detail.json (detail=False: a plain run, no file)"""
     fd = fd if fd is not None else _JSON_FD[0]
-    detail = write_detail(out) if "metric" in out else None
+    detail = write_detail(out) if detail and "metric" in out else None
     line = json.dumps(compact_line(out, detail)) + "\n"
     if fd is None:
         sys.stdout.write(line)
         sys.stdout.flush()
     else:
         os.write(fd, line.encode())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, result, num_envs, seed=0):
+    """--dump-outputs: what the last timed task.step() returned to its caller -- every tensor of the observation dict, the
+    rewards, terminations and truncations (and any tensor in the infos) -- as <dirname>/<name>.npy: float64 stays float64, 32- and
+    64-bit integers become float64 (exact), everything else float32.  Empty tensors (a 0-wide privileged observation) hold no
+    values and are not written.  Above DUMP_LIMIT_BYTES in all, every array with one row per
+    env keeps the same fixed, seeded sample of env rows (ascending env index).  Returns {name: shape}."""
+    import numpy as np
+
+    obs, rew, term, trunc, infos = result
+    tensors = {}
+    for k, v in list(obs.items()) + [("rewards", rew), ("terminations", term), ("truncations", trunc)]:
+        if torch.is_tensor(v) and v.numel():
+            tensors.setdefault(k, v)
+    for k, v in (infos or {}).items():
+        if torch.is_tensor(v) and v.numel():
+            tensors.setdefault("infos_" + k, v)
+    arrays = {}
+    for k, v in tensors.items():
+        wide = v.dtype in (torch.float64, torch.int32, torch.int64, torch.uint32, torch.uint64)
+        arrays["".join(c if c.isalnum() or c in "_-." else "_" for c in k)] = v.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        per_env = sum(a.nbytes for a in arrays.values() if a.ndim and a.shape[0] == num_envs) / num_envs
+        fixed = total - per_env * num_envs
+        keep = max(1, min(num_envs, int((DUMP_LIMIT_BYTES - fixed) // per_env)))
+        idx = np.sort(np.random.default_rng(seed).choice(num_envs, keep, replace=False))
+        arrays = {k: (a[idx] if a.ndim and a.shape[0] == num_envs else a) for k, a in arrays.items()}
+        print(f"[bench] --dump-outputs: {total / 2**20:.1f} MiB of outputs, a seeded sample of {keep} of {num_envs} envs written",
+              file=sys.stderr, flush=True)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def usable_cpus():
@@ -1261,7 +1315,7 @@ def main():
         dist.destroy_process_group()
         return
     preflight = None
-    if use_dist and args.preflight_steps > 0 and (world > 1 or os.environ.get("AGX_BENCH_PREFLIGHT") == "1"):
+    if args.full and use_dist and args.preflight_steps > 0 and (world > 1 or os.environ.get("AGX_BENCH_PREFLIGHT") == "1"):
         # first contact with an N-GPU node: which backend, which stage, which rank pair -- before the first timed step
         preflight = []
         exchange_selftest(args, world, rank, device, limit_s=180.0, preflight=preflight)  # (a first RCCL communicator can take tens of seconds)
@@ -1286,28 +1340,31 @@ def main():
               file=sys.stderr, flush=True)
         if comm_ranks != max(world, 1) or comm_rank != rank:
             raise SystemExit(f"the step exchange's communicator reports rank {comm_rank} of {comm_ranks}; the job is rank {rank} of {world}")
-    # Right after reset() every episode is at step 0: a region shorter than episode_len contains no reset at all.  That number is
-    # measured first and kept as `value_synchronised_episodes` (rounds 1-4 reported it as `value` on short runs); then the episodes
-    # are spread uniformly over their length -- the steady state of a long-running job -- and THAT is what `value` times.
-    sync_steps = max(1, min(args.steps, 100))
-    sync_warm = min(args.warmup, 50)
+    # Right after reset() every episode is at step 0: a region shorter than episode_len contains no reset at all.  With --full that
+    # number is measured first and kept as `value_synchronised_episodes` (rounds 1-4 reported it as `value` on short runs); then the
+    # episodes are spread uniformly over their length -- the steady state of a long-running job -- and THAT is what `value` times.
     ep0 = int(task.sim_env.global_tensor_dict["episode_count"].sum().item())
-    dts_sync = sorted(timed_steps(task, actions, sync_steps, sync_warm if r == 0 else 0, world, gather_buf, overlap=not args.sync_gather)
-                      for r in range(3))
-    sync_resets, ep0 = resets_per_step(task, ep0, sync_warm + 3 * sync_steps)
+    if args.full:
+        sync_steps = max(1, min(args.steps, 100))
+        sync_warm = min(args.warmup, 50)
+        dts_sync = sorted(timed_steps(task, actions, sync_steps, sync_warm if r == 0 else 0, world, gather_buf, overlap=not args.sync_gather)
+                          for r in range(3))
+        sync_resets, ep0 = resets_per_step(task, ep0, sync_warm + 3 * sync_steps)
     desync = desynchronise_episodes(task)
     # `value` = the MEDIAN of `--regions` timed regions of exactly `--steps` steps each (each bracketed by barrier + device
-    # synchronize, maximum over ranks); minimum and maximum are reported next to it.  One region of the driver's 20 steps lasts
-    # 0.25 ms: a single scheduler hiccup is +-30 % of it.
+    # synchronize, maximum over ranks); minimum and maximum are reported next to it.  A plain run times one region; one region
+    # of the driver's 20 steps lasts 0.25 ms: a single scheduler hiccup is +-30 % of it.
     dts, hosts = [], []
     for r in range(max(1, args.regions)):
         dts.append(timed_steps(task, actions, args.steps, args.warmup if r == 0 else 0, world, gather_buf, overlap=not args.sync_gather))
         hosts.append(timed_steps.last_host_s)
+    if args.dump_outputs and rank == 0 and timed_steps.last_result is not None:
+        dump_outputs(args.dump_outputs, timed_steps.last_result, N)
     desync["measured_resets_per_step"], ep0 = resets_per_step(task, ep0, args.warmup + len(dts) * args.steps)
     dts_sorted = sorted(dts)
     dt = dts_sorted[len(dts_sorted) // 2]
     value = n_gpus * N * args.steps / dt
-    exchange = exchange_diagnostics(task, actions, args, world, gather_buf, dt) if use_dist else None
+    exchange = exchange_diagnostics(task, actions, args, world, gather_buf, dt) if use_dist and args.full else None
     out = {
         "metric": f"env-steps/sec at N_envs={N} per GPU (" + ("dynamics-only" if args.workload == "dynamics" else "+" + args.workload + " sensor") + ")",
         "value": value,
@@ -1322,11 +1379,6 @@ def main():
         "value_is": "steady state with de-synchronised episodes: num_envs / episode_len envs reset in EVERY timed step (since round 5; rounds 1-4 "
                     "timed short regions right after reset(), where no env resets: that figure is `value_synchronised_episodes`)",
         "episodes": dict(desync, state="de-synchronised (steady state: resets in every step)"),
-        "value_synchronised_episodes": n_gpus * N * sync_steps / dts_sync[1],
-        "synchronised_episodes": {"ms_per_step": [1e3 * x / sync_steps for x in dts_sync], "steps_each": sync_steps, "regions": 3,
-                                  "measured_resets_per_step": sync_resets,
-                                  "note": "every episode at the same step (right after reset()): no env truncates inside these regions -- "
-                                          "the reset branch of the step's second launch does no work; what rounds 1-4 reported for short runs"},
         "host": {"enqueue_us_per_step": sorted(1e6 * h / args.steps for h in hosts)[len(hosts) // 2],
                  "share_of_step": sorted(h / d for h, d in zip(hosts, dts))[len(hosts) // 2],
                  "note": "wall time of the Python loop that enqueues a region's launches (before the closing synchronize) over the region's "
@@ -1350,6 +1402,20 @@ def main():
             "rng": "strict (reference torch stream, host sync/step)" if args.strict_rng else "sync-free (device Philox4x32-10)",
         },
     }
+    if not args.full:  # the plain run: the headline figure and nothing else
+        if rank == 0:
+            emit_line(out, json_fd, detail=False)
+        if use_dist:
+            import torch.distributed as dist
+
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    out["value_synchronised_episodes"] = n_gpus * N * sync_steps / dts_sync[1]
+    out["synchronised_episodes"] = {"ms_per_step": [1e3 * x / sync_steps for x in dts_sync], "steps_each": sync_steps, "regions": 3,
+                                    "measured_resets_per_step": sync_resets,
+                                    "note": "every episode at the same step (right after reset()): no env truncates inside these regions -- "
+                                            "the reset branch of the step's second launch does no work; what rounds 1-4 reported for short runs"}
     copy_gbs = hbm_copy_gbs(device) if rank == 0 else None
     if rank == 0 and args.workload == "dynamics":
         timing, k = kernel_time_dynamics(task, actions)

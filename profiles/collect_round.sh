@@ -15,8 +15,8 @@ done
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${R}_prof_default -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1000 --warmup 100 --no-cpu-baseline > $OUT/${R}_bench_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${R}_prof_lidar -o p -- python $GRAFT_REPO_ROOT/bench.py --workload lidar --steps 60 --warmup 6 > $OUT/${R}_bench_lidar_under_rocprof.json 2>/dev/null
 cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err
-timeout 300 python bench.py --workload depth --steps 200 --warmup 20 > $OUT/${R}_bench_depth.json 2>/dev/null
-timeout 300 python bench.py --workload lidar --steps 100 --warmup 10 > $OUT/${R}_bench_lidar.json 2>/dev/null
-timeout 300 python bench.py --workload lidar_nav --steps 200 --warmup 20 > $OUT/${R}_bench_lidar_nav.json 2>/dev/null
+timeout 600 python bench.py --full > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err
+timeout 300 python bench.py --full --workload depth --steps 200 --warmup 20 > $OUT/${R}_bench_depth.json 2>/dev/null
+timeout 300 python bench.py --full --workload lidar --steps 100 --warmup 10 > $OUT/${R}_bench_lidar.json 2>/dev/null
+timeout 300 python bench.py --full --workload lidar_nav --steps 200 --warmup 20 > $OUT/${R}_bench_lidar_nav.json 2>/dev/null
 ls $OUT | grep ${R}_ | head -40

@@ -7,15 +7,15 @@ set -u
 O=gpurun_out/r06m
 mkdir -p $O
 export TMPDIR=/tmp
-run() { name=$1; shift; python bench.py "$@" > $O/$name.json 2> $O/$name.err; cp gpurun_out/bench_detail.json $O/${name}_detail.json 2>/dev/null; }
+run() { name=$1; shift; python bench.py --full "$@" > $O/$name.json 2> $O/$name.err; cp bench_detail.json $O/${name}_detail.json 2>/dev/null; }
 run bench_default
 run bench_driver_style --steps 20 --warmup 5
 run bench_depth --workload depth --steps 200 --warmup 20
 run bench_lidar --workload lidar --steps 100 --warmup 10
 run bench_lidar_velocity --workload lidar_velocity --steps 100 --warmup 10
 run bench_lidar_nav --workload lidar_nav --steps 200 --warmup 20
-AGX_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --no-lidar --no-strict > $O/bench_forced_dist_world1.json 2> $O/bench_forced_dist.err
-cp gpurun_out/bench_detail.json $O/bench_forced_dist_world1_detail.json 2>/dev/null
+AGX_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --no-lidar --no-strict > $O/bench_forced_dist_world1.json 2> $O/bench_forced_dist.err
+cp bench_detail.json $O/bench_forced_dist_world1_detail.json 2>/dev/null
 python bench.py --gpus 1 --exchange-selftest-only > $O/exchange_selftest_world1.jsonl 2> $O/exchange_selftest.err
 PYTHONPATH=. python examples/benchmark.py --steps 5000 > $O/reference_benchmark_recipe.txt 2>/dev/null
 PYTHONPATH=. python examples/benchmark.py --rendering --steps 2000 >> $O/reference_benchmark_recipe.txt 2>/dev/null

@@ -50,3 +50,17 @@ def random_robot_states(n, seed, lo, hi, tilt=0.4):
     e = rng.uniform(-1, 1, (n, 3)) * np.array([tilt, tilt, np.pi])
     s[:, 3:7] = quat_from_euler(e.astype(np.float32))
     return s
+
+
+def golden_environment_assets(dest):
+    """Writes the reference's obstacle URDFs kept in tests/golden/environment_assets.npz (oracle/gen_golden_environment_assets.py)
+    back out as <dest>/{objects,panels,walls,trees,thin}/*.urdf and returns dest."""
+    import os
+
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "environment_assets.npz"))
+    for key in g.files:
+        sub, name = key.split("__", 1)
+        os.makedirs(os.path.join(dest, sub), exist_ok=True)
+        with open(os.path.join(dest, sub, name), "w") as f:
+            f.write(str(g[key]))
+    return str(dest)

@@ -39,12 +39,12 @@ def test_graft_entry_build_runs_on_cpu():
     assert os.path.exists(entry.build())
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """sizeof of the ctypes mirrors == sizeof in C (compiled with gcc from the header)."""
     from aerial_gym_simulator_amd import _lib
 
     src = '#include <stdio.h>\n#include "aerial_gym_hip.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(AgxRobotParams), sizeof(AgxEnvBuffers), sizeof(AgxResetArgs));printf("%zu %zu %zu %zu\\n", sizeof(AgxTaskArgs), sizeof(AgxRangeLimits), sizeof(AgxPositionStepPlan), sizeof(AgxImuArgs));printf("%zu %zu %zu\\n", sizeof(AgxNavRobotSideArgs), sizeof(AgxRobotStepArgs), sizeof(AgxLinkFrames));printf("%zu\\n", sizeof(AgxStrictStepPlan));return 0;}'
-    exe = "/tmp/agx_sizeof"
+    exe = str(tmp_path / "agx_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src, text=True, check=True)
     sizes = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
     assert sizes == [ctypes.sizeof(_lib.AgxRobotParams), ctypes.sizeof(_lib.AgxEnvBuffers), ctypes.sizeof(_lib.AgxResetArgs),

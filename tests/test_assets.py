@@ -1,11 +1,18 @@
 """CPU: box obstacles from URDF files (box subset) and the restated box-size tables
-checked against the reference's own URDFs when the reference tree is present (build container)."""
+checked against the reference's own URDFs (tests/golden/environment_assets.npz: the reference's
+resources/models/environment_assets/{objects,panels,walls} and the first 25 of its trees / thin files)."""
 import os
 
 import numpy as np
 import pytest
 
-REF_ASSETS = "/root/reference/resources/models/environment_assets"
+
+@pytest.fixture(scope="module")
+def ref_assets(tmp_path_factory):
+    from scene_util import golden_environment_assets
+
+    return golden_environment_assets(tmp_path_factory.mktemp("environment_assets"))
+
 
 BOX_URDF = """<?xml version='1.0'?>
 <robot name="box"><link name="base_link">
@@ -74,30 +81,29 @@ def test_scene_from_a_urdf_folder(tmp_path):
     assert rods.min() >= 3 and rods.max() < 23  # the three fixed rods + a random share of the folder picks
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference tree not present (GPU box)")
-def test_restated_box_tables_match_the_reference_urdfs():
+def test_restated_box_tables_match_the_reference_urdfs(ref_assets):
     """config/asset_config.py restates the reference's obstacle URDFs as data: every shipped box file must be in
     the table of its asset type, and nothing else."""
     from aerial_gym_simulator_amd.assets import list_urdf_files, parse_box_urdf
     from aerial_gym_simulator_amd.config import asset_config as A
 
     def sizes(folder):
-        return sorted(parse_box_urdf(os.path.join(REF_ASSETS, folder, f)).size for f in list_urdf_files(os.path.join(REF_ASSETS, folder)))
+        return sorted(parse_box_urdf(os.path.join(ref_assets, folder, f)).size for f in list_urdf_files(os.path.join(ref_assets, folder)))
 
     assert sizes("objects") == sorted(tuple(float(v) for v in s) for s in A.object_asset_params.box_sizes)
     assert sizes("panels") == sorted(tuple(float(v) for v in s) for s in A.panel_asset_params.box_sizes)
     walls = {w.__name__: tuple(float(v) for v in w.box_sizes[0]) for w in (A.left_wall, A.right_wall, A.top_wall, A.bottom_wall, A.front_wall, A.back_wall)}
     for name, size in walls.items():
-        assert parse_box_urdf(os.path.join(REF_ASSETS, "walls", name + ".urdf")).size == size, name
+        assert parse_box_urdf(os.path.join(ref_assets, "walls", name + ".urdf")).size == size, name
     # the same env built from the reference's folders and from the restated tables has the same box multiset
     from aerial_gym_simulator_amd.config.env_config import EnvWithObstaclesCfg
     from aerial_gym_simulator_amd.env_manager.scene_manager import SceneManager
 
     class ref_objects(A.object_asset_params):
-        asset_folder = os.path.join(REF_ASSETS, "objects")
+        asset_folder = os.path.join(ref_assets, "objects")
 
     class ref_panels(A.panel_asset_params):
-        asset_folder, file = os.path.join(REF_ASSETS, "panels"), "panel.urdf"
+        asset_folder, file = os.path.join(ref_assets, "panels"), "panel.urdf"
 
     class Cfg(EnvWithObstaclesCfg):
         class env_config:
@@ -109,7 +115,7 @@ def test_restated_box_tables_match_the_reference_urdfs():
     assert {tuple(s) for s in a._np["size"].reshape(-1, 3)} == {tuple(s) for s in b._np["size"].reshape(-1, 3)}
     # with the trees / thin sets (cylinders) the loader says what is missing instead of guessing
     with pytest.raises(NotImplementedError):
-        parse_box_urdf(os.path.join(REF_ASSETS, "trees", "tree_0.urdf"))
+        parse_box_urdf(os.path.join(ref_assets, "trees", "tree_0.urdf"))
 
 
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", "assets")
@@ -204,14 +210,13 @@ def test_multi_primitive_scene_layout():
     assert SceneManager(EnvWithObstaclesCfg, 2, "cpu", None, box_objects=False).bvh_prims_per_object == 12
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference tree not present (GPU box)")
-def test_reference_trees_and_thin_sets_load():
+def test_reference_trees_and_thin_sets_load(ref_assets):
     from aerial_gym_simulator_amd.assets import list_urdf_files, load_urdf_primitives
 
     for sub, n_prims in (("trees", 13), ("thin", 1)):
-        files = list_urdf_files(os.path.join(REF_ASSETS, sub))
+        files = list_urdf_files(os.path.join(ref_assets, sub))
         for f in files[:25]:
-            ps = load_urdf_primitives(os.path.join(REF_ASSETS, sub, f))
+            ps = load_urdf_primitives(os.path.join(ref_assets, sub, f))
             assert len(ps) == n_prims and all(np.isfinite(p.T).all() for p in ps)
 
 
@@ -315,9 +320,8 @@ def test_forest_env_scene_arrays_at_reference_size_from_the_fixture_tree():
     _check_forest_scene_arrays(sc, 4)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference tree not present (GPU box)")
-def test_forest_env_scene_arrays_from_the_reference_resources():
-    """forest_env built from the reference's own resources/models/environment_assets/trees (100 files, one
-    drawn per env) on the CPU box: the same array checks as the fixture tree"""
-    sc = _forest_scene(os.path.join(REF_ASSETS, "trees"), n_envs=6)
+def test_forest_env_scene_arrays_from_the_reference_resources(ref_assets):
+    """forest_env built from the reference's own resources/models/environment_assets/trees (25 of its 100
+    files, tests/golden/environment_assets.npz, one drawn per env): the same array checks as the fixture tree"""
+    sc = _forest_scene(os.path.join(ref_assets, "trees"), n_envs=6)
     _check_forest_scene_arrays(sc, 6)

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,11 +89,11 @@ def test_exchange_selftest_only_prints_one_verdict_per_backend():
 
 @pytest.mark.gpu
 def test_sharded_run_starts_with_the_exchange_preflight():
-    """whatever command a multi-GPU lease runs first, the exchange verdicts come first.  A timed run with more
+    """whatever command a multi-GPU lease runs first, the exchange verdicts come first.  A --full timed run with more
     than one rank (here: the sharded code path in a world of one, AGX_BENCH_FORCE_DIST + AGX_BENCH_PREFLIGHT) runs
     `--preflight-steps` checksum-verified exchange steps per backend before anything is timed: verdicts on stderr, their summary in
     the ONE stdout line (`exchange.preflight`), the timed legs after it."""
-    r = run_bench(["--gpus", "1", "--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-depth", "--no-lidar", "--no-strict",
+    r = run_bench(["--gpus", "1", "--steps", "50", "--warmup", "10", "--full", "--no-cpu-baseline", "--no-depth", "--no-lidar", "--no-strict",
                    "--preflight-steps", "60"], {"AGX_BENCH_FORCE_DIST": "1", "AGX_BENCH_PREFLIGHT": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     (line,) = json_lines(r.stdout)
@@ -101,6 +102,60 @@ def test_sharded_run_starts_with_the_exchange_preflight():
     assert all(p["ok"] is True and p["steps"] == 60 and p["first_failure"] is None for p in pre), pre
     assert r.stderr.count("[bench preflight]") == 3
     assert line["value"] > 1e6 and len(r.stdout) < 8192
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_the_steps_asked_and_dumps_the_same_outputs(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps, prints the contract's keys and nothing measured
+    beside them, writes no bench_detail.json, and --dump-outputs writes the last timed step's outputs: two runs with the same
+    arguments write the same arrays, bit for bit."""
+    argv = ["--gpus", "1", "--steps", "30", "--warmup", "5"]
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = run_bench(argv + ["--dump-outputs", str(d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        (line,) = json_lines(r.stdout)
+        lines.append(line)
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in a, k
+    assert a["steps"] == 30 and a["warmup"] == 5 and a["timed_regions"]["count"] == 1 and a["higher_is_better"] is True
+    assert a["value"] == pytest.approx(8192 / (a["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not ({"roofline", "cpu_baseline", "plus_depth", "plus_lidar", "parity", "value_strict_rng", "detail"} & set(a)), sorted(a)
+    assert set(dumps[0]) >= {"observations.npy", "rewards.npy", "terminations.npy", "truncations.npy"}
+    assert dumps[0]["observations.npy"].shape == (8192, 13) and dumps[0]["rewards.npy"].shape == (8192,)
+    assert sum(x.nbytes for x in dumps[0].values()) <= 64 << 20
+    assert set(dumps[0]) == set(dumps[1])
+    for name, x in dumps[0].items():
+        assert x.dtype in (np.float32, np.float64) and x.size > 0 and np.array_equal(x, dumps[1][name]), name
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs on CPU tensors of the task's return shape: names, dtypes (float64 kept, integers exact), and above the size
+    limit the same seeded sample of env rows in every per-env array"""
+    import torch
+
+    bench = _bench_module()
+    n = 1000
+    obs = {"observations": torch.arange(n * 3, dtype=torch.float32).reshape(n, 3), "terminations": torch.zeros(n, dtype=torch.uint8),
+           "priviliged_obs": torch.zeros(n, 0)}
+    res = (obs, torch.arange(n, dtype=torch.float64), obs["terminations"], torch.ones(n, dtype=torch.bool), {"steps": torch.arange(n, dtype=torch.int64) + (1 << 40)})
+    shapes = bench.dump_outputs(str(tmp_path / "all"), res, n)
+    assert shapes == {"observations": [n, 3], "terminations": [n], "rewards": [n], "truncations": [n], "infos_steps": [n]}  # nothing empty
+    assert not (tmp_path / "all" / "priviliged_obs.npy").exists()
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in shapes}
+    assert got["observations"].dtype == np.float32 and got["rewards"].dtype == np.float64 and got["infos_steps"].dtype == np.float64
+    assert got["infos_steps"][-1] == (1 << 40) + n - 1 and got["truncations"].dtype == np.float32 and got["truncations"].all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 100)
+    s1 = bench.dump_outputs(str(tmp_path / "s1"), res, n)
+    s2 = bench.dump_outputs(str(tmp_path / "s2"), res, n)
+    assert s1 == s2 and 0 < s1["rewards"][0] < n
+    k1, k2 = np.load(tmp_path / "s1" / "rewards.npy"), np.load(tmp_path / "s2" / "rewards.npy")
+    assert np.array_equal(k1, k2) and np.all(np.diff(k1) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "observations.npy")[:, 0], 3 * k1)
+    assert sum(np.load(tmp_path / "s1" / (k + ".npy")).nbytes for k in s1) <= 16 * 100
 
 
 def _bench_module():

@@ -176,13 +176,18 @@ def test_mesh_and_sphere_obstacles_images_and_collisions(orc):
     assert crash_ref.all() and npy(g["crashes"]).all()
 
 
-def test_reference_tree_assets_when_present():
-    """with AERIAL_GYM_RESOURCES pointing at the reference's resources, forest_env loads its 13-link cylinder trees"""
+def test_reference_tree_assets_when_present(monkeypatch, tmp_path):
+    """forest_env loads the reference's 13-link cylinder trees: from AERIAL_GYM_RESOURCES when it points at the reference's
+    resources, else from 25 of them kept in tests/golden/environment_assets.npz"""
+    import aerial_gym_simulator_amd  # noqa: F401
+    from aerial_gym_simulator_amd.config import asset_config as A
+    from aerial_gym_simulator_amd.sim.sim_builder import SimBuilder
+
     res = os.environ.get("AERIAL_GYM_RESOURCES", "")
     if not os.path.isdir(os.path.join(res, "models", "environment_assets", "trees")):
-        pytest.skip("AERIAL_GYM_RESOURCES not set to a resources tree with the `trees` set")
-    import aerial_gym_simulator_amd  # noqa: F401
-    from aerial_gym_simulator_amd.sim.sim_builder import SimBuilder
+        from scene_util import golden_environment_assets
+
+        monkeypatch.setattr(A.tree_asset_params, "asset_folder", os.path.join(golden_environment_assets(tmp_path), "trees"))
 
     env = SimBuilder().build_env("base_sim", "forest_env", "base_quadrotor_with_camera_64x48", "lee_velocity_control", DEV, num_envs=8)
     assert env.scene.num_prims == 1 + 13 + 35
