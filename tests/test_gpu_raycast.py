@@ -634,13 +634,15 @@ def test_bvh_object_level_order_equals_the_full_key_sort(orc):
 
 
 def _walk_tree(nodes, NI, tris_e, e, nt):
-    """-> (times each triangle is reached, object nodes, internal nodes visited); checks every child box on the way"""
+    """-> (times each triangle is reached, object nodes, internal nodes visited, internal levels on the longest path from the
+    root); checks every child box on the way"""
     OBJ = 0x40000000
     seen = np.zeros(nt, int)
-    stack, visited, objects = [0], 0, 0
+    stack, visited, objects, depth = [(0, 1)], 0, 0, 0
     while stack:
-        i = stack.pop()
+        i, level = stack.pop()
         visited += 1
+        depth = max(depth, level)
         assert 0 <= i < nt - 1
         for cslot, sslot, lo, hi in ((3, 11, slice(0, 3), slice(4, 7)), (7, 15, slice(8, 11), slice(12, 15))):
             c, s2 = int(NI[e, i, cslot]), int(NI[e, i, sslot])
@@ -656,8 +658,8 @@ def _walk_tree(nodes, NI, tris_e, e, nt):
                 seen[f0:f0 + 12] += 1
                 objects += 1
             else:
-                stack.append(c)
-    return seen, objects, visited
+                stack.append((c, level + 1))
+    return seen, objects, visited, depth
 
 
 def test_object_level_build_with_parked_and_non_box_objects(orc):
@@ -679,7 +681,7 @@ def test_object_level_build_with_parked_and_non_box_objects(orc):
             nodes = S.nodes.cpu().numpy()
             tris = S.tri_world.cpu().numpy().reshape(n, -1, 3, 3)
             for e in range(n):
-                seen, objects, visited = _walk_tree(nodes, nodes.view(np.int32), tris[e], e, S.nt)
+                seen, objects, visited, _ = _walk_tree(nodes, nodes.view(np.int32), tris[e], e, S.nt)
                 assert seen.min() == 1 and seen.max() == 1
                 assert objects == 9 and visited == (k - 1) + 5 * (k - 9)
         _, _, _, _, pos, quat = _poses(orc, n, sc, 5)

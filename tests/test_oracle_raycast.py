@@ -321,3 +321,131 @@ def test_sensor_mount_and_pose_match_a_real_reference_sensor(orc, tag):
     pos, quat = orc.sensor_pose(state, lpos, lquat, g["pose_%s_frame_quat" % tag])
     assert np.abs(pos - g["pose_%s_sensor_position" % tag]).max() < 1e-6
     assert np.abs(quat - g["pose_%s_sensor_orientation" % tag]).max() < 3e-7
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The adversarial scene generators of tests/test_gpu_bvh_limits.py: they deliver what they promise, and the oracle's brute force
+# (the GPU file's reference) agrees with a float64 closest hit on them.
+def _morton_object_codes(tris_e, K):
+    """the object-level build's 30-bit sort codes (csrc/agx_scene.hip bvh_build_objects_env), restated in float32 numpy: AABB
+    centres of the objects not parked (tri_parked: the first vertex below -900 m in x, y and z), 10-bit grid over their bounds,
+    low three bits masked"""
+    v = tris_e.reshape(K, 36, 3)
+    alo, ahi = v.min(1), v.max(1)
+    cen = np.float32(0.5) * (alo + ahi)
+    parked = (tris_e.reshape(K, 12, 9)[:, 0, 0:3] < -900).all(1)
+    blo, bhi = cen[~parked].min(0), cen[~parked].max(0)
+    ext = bhi - blo
+    inv = np.where(ext > 0, np.float32(1023) / np.where(ext > 0, ext, 1), 0).astype(np.float32)
+    qv = np.clip((cen - blo) * inv, 0, 1023).astype(np.uint32)
+
+    def expand(x):
+        x = (x * 0x00010001) & 0xFF0000FF
+        x = (x * 0x00000101) & 0x0F00F00F
+        x = (x * 0x00000011) & 0xC30C30C3
+        return (x * 0x00000005) & 0x49249249
+
+    qv = qv.astype(np.uint64)
+    code = (expand(qv[:, 0]) << 2) | (expand(qv[:, 1]) << 1) | expand(qv[:, 2])
+    return code & ~np.uint64(7), parked
+
+
+def test_adversarial_scene_generators(orc):
+    import scene_util as su
+
+    # explicit boxes: the transformed corners are where float64 puts them
+    rng = np.random.default_rng(0)
+    c, q, e = su.random_rotated_boxes(rng, 2, 9, [-3, -3, -3], [3, 3, 3])
+    sc = su.box_scene(c, q, e)
+    tw = orc.scene_transform(sc["tri_local"], sc["tri_asset"], sc["asset_state"])
+    want = c[0][:, None].astype(np.float64) + np.einsum("kij,kvj->kvi", su.quat_matrix(q[0]), su.CORNER_SIGNS[None] * e[0][:, None] * 0.5)
+    assert np.abs(su.box_corners_world(tw[0], 9) - want).max() < 1e-5
+    assert np.abs(np.linalg.norm(su.random_quats(rng, (1000,)), axis=-1) - 1).max() < 1e-6
+
+    # aimed boxes: the chosen corner lies on its ray, or the chosen edge crosses it, off by the stated float32 ulps or across by
+    # kBoxEps +- delta.  The ulp offsets are nominal: they move the float64 centre, which is then rounded to float32 and goes through
+    # the float32 scene transform -- a few ulps more either way -- so the check allows 6 ulps (an exact aim, 0, is within 6, too)
+    sc, rv, origin, aim = su.aimed_scene()
+    n, K = sc["asset_state"].shape[:2]
+    tw = orc.scene_transform(sc["tri_local"], sc["tri_asset"], sc["asset_state"]).reshape(n, -1, 9)
+    dirs = rv.reshape(-1, 3)[:K].astype(np.float64)
+    is_corner = (np.abs(aim["point"]) == 1).all(-1)
+    is_edge = (np.abs(aim["point"]) == 1).sum(-1) == 2
+    for name in ("exact", "ulps", "box tolerance", "ulps at 1 km", "ulps at 5 km"):  # (the others move box 0 onto the origin)
+        env = su.AIM_ENVS.index(name)
+        corners = su.box_corners_world(tw[env], K).astype(np.float64)
+        ulp = np.array([np.spacing(np.float32(np.abs(origin[env] + aim["t"][env, k] * dirs[k]).max())) for k in range(K)], np.float64)
+        for kind, ks in (("corner", np.flatnonzero(is_corner[env])), ("edge", np.flatnonzero(is_edge[env]))):
+            assert len(ks) > 50
+            pt = aim["point"][env, ks]
+            lo_i = ((np.where(np.abs(pt) == 1, pt, -1) > 0) * np.array([4, 2, 1])).sum(1)  # the corner, or the edge's lower end
+            hi_i = ((np.where(np.abs(pt) == 1, pt, 1) > 0) * np.array([4, 2, 1])).sum(1)  # the edge's upper end
+            p = corners[ks, lo_i] - origin[env].astype(np.float64)
+            if kind == "corner":  # distance of the corner from the ray; the shift is perpendicular to the ray
+                off = p - (p * dirs[ks]).sum(1, keepdims=True) * dirs[ks]
+                dist, stated = np.linalg.norm(off, axis=1), np.linalg.norm(aim["shift"][env, ks], axis=1)
+            else:  # distance between the ray and the edge's line; of the shift, what lies along their common normal
+                nrm = np.cross(dirs[ks], corners[ks, hi_i] - corners[ks, lo_i])
+                nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+                dist, stated = np.abs((p * nrm).sum(1)), np.abs((aim["shift"][env, ks] * nrm).sum(1))
+            if name == "box tolerance":
+                assert np.abs(dist - stated).max() < 1e-6, kind
+                if kind == "corner":
+                    assert np.allclose(stated, su.BOX_EPS, rtol=0.11)
+            else:
+                assert np.array_equal(np.linalg.norm(aim["shift"][env, ks], axis=1) == 0, aim["ulps"][env, ks] == 0)
+                want = stated if kind == "edge" else np.abs(aim["ulps"][env, ks]) * ulp[ks]
+                assert np.all(np.abs(dist - want) <= 6 * ulp[ks]), (name, kind)
+
+    # key degeneracies: parked counts, equal centres, the chain of single-bit Morton codes
+    for K in (129, 245):
+        names, sc, deformed = su.degenerate_scenes(np.random.default_rng(77 + K), K)
+        tw = orc.scene_transform(sc["tri_local"], sc["tri_asset"], sc["asset_state"])
+        parked = (tw.reshape(len(names), K, 12, 9)[..., 0:9].reshape(len(names), K, -1) < -900).all(-1)
+        assert list(parked.sum(1)) == [0, 0, 0, K, K - 1, K - 2, 0, 0]
+        assert len(np.unique(sc["asset_state"][0, :, 0:3], axis=0)) == 1
+        assert len(np.unique(sc["asset_state"][1, :, 0:3], axis=0)) == 2
+        assert deformed[7].sum() == (K + 1) // 2
+        corner1 = su.BOX_VERTS[1] * sc["half"][7, :, None, :] * 2  # vertex 0 of triangle 0 is corner 1 of a box
+        moved = ~np.all(sc["tri_local"][7].reshape(K, 12, 9)[:, 0, 0:3] == corner1[:, 0], axis=-1)
+        assert np.array_equal(moved, deformed[7])
+        code, pk = _morton_object_codes(tw[names.index("geometric progression")], K)
+        assert not pk.any()
+        chain = sorted(int(x) for x in code if x and x != code.max())
+        assert chain == [1 << b for b in range(3, 30)]  # 27 codes of one bit each: every one shares a longer prefix with 0
+        assert (code == 0).sum() == K - 28
+
+
+def test_oracle_brute_force_matches_float64_on_adversarial_scenes(orc):
+    """the brute force the GPU file compares with against an independent float64 Moller-Trumbore, on the rays whose answer is
+    unambiguous (scene_util.closest_hit_f64): hit / miss and segment id; where the ray meets its triangle at an incidence cosine
+    >= 0.5, |t - t64| <= 2e-6 (t + L) + 1.2e-7 t, L the triangle's diameter (derivation at scene_util.t64_bound)"""
+    import scene_util as su
+
+    sc, rv, origin, _ = su.aimed_scene()
+    n = sc["asset_state"].shape[0]
+    K = sc["asset_state"].shape[1]
+    tw = orc.scene_transform(sc["tri_local"], sc["tri_asset"], sc["asset_state"])
+    quat = np.tile(np.float32([0, 0, 0, 1]), (n, 1, 1))
+    far = 100.0
+    px, seg = orc.raycast_lidar(rv, far, "range", origin.reshape(n, 1, 3), quat, tw, sc["tri_seg"])
+    names, dsc, _ = su.degenerate_scenes(np.random.default_rng(77 + 129), 129)
+    dtw = orc.scene_transform(dsc["tri_local"], dsc["tri_asset"], dsc["asset_state"])
+    dpos = np.tile(np.float32([-8.0, 0.5, 0.8]), (len(names), 1, 1))
+    drv = su.ray_table(np.random.default_rng(2))
+    dpx, dseg = orc.raycast_lidar(drv, far, "range", dpos, quat[:1].repeat(len(names), 0), dtw, dsc["tri_seg"])
+    checked = timed = 0
+    for o, dirs, tris, segs, ora_t, ora_s in [(origin[e], rv.reshape(-1, 3), tw[e], sc["tri_seg"][e], px[e, 0], seg[e, 0]) for e in range(n)] + \
+            [(dpos[e, 0], drv.reshape(-1, 3), dtw[e], dsc["tri_seg"][e], dpx[e, 0], dseg[e, 0]) for e in (0, 1, 2, 6, 7)]:
+        t64, f64, clean, cos, diam = su.closest_hit_f64(o, dirs, tris, far)
+        ora_t, ora_s = ora_t.reshape(-1), ora_s.reshape(-1)
+        hit = np.isfinite(t64)
+        assert np.array_equal((ora_s >= 0)[clean], hit[clean])
+        assert np.array_equal(ora_s[clean & hit], segs[f64[clean & hit]])
+        h = clean & hit & (cos >= su.T64_MIN_COS)
+        err = np.abs(ora_t[h].astype(np.float64) - t64[h])
+        assert (err <= 2e-6 * (t64[h] + diam[h]) + 1.2e-7 * t64[h]).all(), (err / su.t64_bound(t64[h], diam[h])).max()
+        checked += int(clean.sum())
+        timed += int(h.sum())
+    assert checked > 0.6 * (n * rv.shape[0] * rv.shape[1] + 5 * drv.shape[0] * drv.shape[1]) and timed > 0.3 * checked
+    assert (seg[:5, 0].reshape(5, -1)[:, :K] >= 0).mean() > 0.5  # the aimed rays hit (or clip) their boxes
