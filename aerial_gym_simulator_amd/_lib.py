@@ -153,6 +153,11 @@ class AgxTaskArgs(C.Structure):
         ("counters", C.c_void_p),
         ("success_radius", C.c_float),
         ("reserved", C.c_int32),
+        ("proof_slots", C.c_void_p),
+        ("proof_record", C.c_void_p),
+        ("proof_violation", C.c_void_p),
+        ("proof_dv", C.c_float),
+        ("proof_mode", C.c_int32),
     ]
 
 
@@ -227,7 +232,30 @@ class AgxPositionStepPlan(C.Structure):
         ("obs", C.c_void_p),
         ("num_envs", C.c_int32),
         ("k_substeps", C.c_int32),
+        ("proof_slots", C.c_void_p),
+        ("proof_record", C.c_void_p),
+        ("proof_violation", C.c_void_p),
+        ("proof_min_tag", C.c_uint32),
+        ("max_lag", C.c_int32),
+        ("captured", C.c_int32),
+        ("slot_run", C.c_int32),
+        ("last_mode", C.c_int32),
+        ("last_reason", C.c_int32),
+        ("mode_count", C.c_uint64 * 3),
+        ("reason_count", C.c_uint64 * 12),
     ]
+
+
+# single-launch position steps (include/aerial_gym_hip.h AgxPositionStepPlan): AGX_STEP_* and AGX_PROOF_* names
+STEP_MODES = ("two", "any", "none")
+PROOF_REASONS = ("proved", "off", "not_covered", "capture", "no_record", "torn", "void", "tag", "reset_no_witness", "may_truncate",
+                 "may_crash", "lag")
+PROOF_HORIZON, PROOF_SLOT_WORDS, PROOF_RECORD_WORDS = 31, 8, 8
+
+
+class AgxStepProofQuery(C.Structure):
+    _fields_ = [("now_tag", C.c_uint32), ("min_tag", C.c_uint32), ("episode_len", C.c_int32), ("reset_on_collision", C.c_int32),
+                ("dt", C.c_float), ("max_linear_velocity", C.c_float), ("dv", C.c_float), ("reserved", C.c_int32)]
 
 
 MAX_UNIFORM_SEGMENTS = 8
@@ -248,7 +276,7 @@ class AgxLinkFrames(C.Structure):
     _fields_ = [("num_bodies", C.c_int32), ("reserved", C.c_int32), ("rot", (C.c_float * 9) * MAX_BODIES), ("pos", (C.c_float * 3) * MAX_BODIES)]
 
 
-ABI_VERSION = 12  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 13  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -281,6 +309,12 @@ _SIGNATURES = {
                                      C.POINTER(AgxNavRobotSideArgs), _P]),
     "agx_post_step_position": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, C.POINTER(AgxResetArgs), _P, _P, _P]),
     "agx_position_task_step": (C.c_int, [C.POINTER(AgxPositionStepPlan), _P, _P]),
+    "agx_step_proof_decide": (C.c_int, [_P, C.POINTER(AgxStepProofQuery), C.POINTER(C.c_int32)]),
+    "agx_step_proof_dv": (C.c_float, [C.POINTER(AgxRobotParams)]),
+    "agx_step_proof_travel": (C.c_float, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "agx_step_proof_witness_bit": (C.c_uint32, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "agx_host_record_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
+    "agx_host_record_free": (C.c_int, [_P]),
     "agx_torch_uniform_fill": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                          C.POINTER(C.c_uint64), _P]),
     "agx_host_word_create": (C.c_int, [C.POINTER(C.POINTER(C.c_uint32))]),
@@ -407,7 +441,8 @@ def binary_matches_sources():
 
 
 def set_option(name, value):
-    """agx_set_option: process-wide tuning / A-B switches of the library ("env_step_quad", "ray_split"; include/aerial_gym_hip.h)"""
+    """agx_set_option: process-wide tuning / A-B switches of the library ("env_step_quad", "ray_split", "single_launch_step";
+    include/aerial_gym_hip.h)"""
     check(load().agx_set_option(name.encode(), int(value)), "agx_set_option")
 
 

@@ -16,12 +16,14 @@ int fail(int code, const char *fmt, ...) {
   va_end(ap);
   return code;
 }
-static std::atomic<int> g_env_step_quad{1}, g_ray_split{0};
+static std::atomic<int> g_env_step_quad{1}, g_ray_split{0}, g_single_launch_step{1};
 int option_env_step_quad() { return g_env_step_quad.load(std::memory_order_relaxed); }
 int option_ray_split() { return g_ray_split.load(std::memory_order_relaxed); }
+int option_single_launch_step() { return g_single_launch_step.load(std::memory_order_relaxed); }
 static std::atomic<int> *option_slot(const char *name, int *lo, int *hi) {
   if (name && !strcmp(name, "env_step_quad")) { *lo = 0; *hi = 1; return &g_env_step_quad; }
   if (name && !strcmp(name, "ray_split")) { *lo = 0; *hi = 1 << 20; return &g_ray_split; }
+  if (name && !strcmp(name, "single_launch_step")) { *lo = 0; *hi = 1; return &g_single_launch_step; }
   return nullptr;
 }
 }  // namespace agx
@@ -29,7 +31,7 @@ static std::atomic<int> *option_slot(const char *name, int *lo, int *hi) {
 extern "C" int agx_set_option(const char *name, int value) {
   int lo, hi;
   std::atomic<int> *slot = agx::option_slot(name, &lo, &hi);
-  AGX_REQUIRE(slot, "agx_set_option: unknown option '%s' (env_step_quad, ray_split)", name ? name : "(null)");
+  AGX_REQUIRE(slot, "agx_set_option: unknown option '%s' (env_step_quad, ray_split, single_launch_step)", name ? name : "(null)");
   AGX_REQUIRE(value >= lo && value <= hi, "agx_set_option: %s = %d outside [%d, %d]", name, value, lo, hi);
   slot->store(value, std::memory_order_relaxed);
   return AGX_OK;

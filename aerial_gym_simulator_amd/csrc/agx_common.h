@@ -22,6 +22,7 @@ inline int check_launch(const char *what) {
 // process-wide options (agx_set_option, agx_api.cpp); read per launch
 int option_env_step_quad();
 int option_ray_split();
+int option_single_launch_step();
 
 inline int blocks_for(int n, int block) { return (n + block - 1) / block; }
 

@@ -46,7 +46,10 @@
 #include "agx_rng.h"
 #include "agx_step_signal.h"
 
+#include <chrono>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #ifndef AGX_DYN_FAST_RCP
@@ -931,117 +934,6 @@ AGX_DEV void quad_integrate(const AgxRobotParams &P, const QuadConsts<M> &C, flo
   }
   v = v_new;
   w = w_new;
-}
-
-__global__ void __launch_bounds__(64, 1)
-    k_env_step_quad_position(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, AgxTaskArgs T) {
-  const int tid = threadIdx.x;
-  const int l = tid & 3, l3 = l < 3 ? l : 2;  // component of a 4-vector / of a 3-vector (lane 3 repeats z: don't care)
-  const int i = blockIdx.x * 16 + (tid >> 2);  // env
-  const unsigned ol = ((unsigned)l * (unsigned)n + (unsigned)i) * 4u, ol3 = ((unsigned)l3 * (unsigned)n + (unsigned)i) * 4u;  // AGX_QAT
-  bool reset = false;
-  if (blockIdx.x == 0) push_publish_previous(B);  // peer push: the previous step's rows have landed everywhere
-  const uint32_t push_peek = blockIdx.x == 0 ? push_wait_peek(B) : 0u;  // ... and this step's slot: looked at when the kernel is done
-  if (i < n) {
-    // ---- loads: one instruction per vector
-    float p = AGX_QAT(B.state, 0, ol3), q = AGX_QAT(B.state, 3, ol), v = AGX_QAT(B.state, 7, ol3), w = AGX_QAT(B.state, 10, ol3);
-    float u[1] = {AGX_QAT(B.motor_thrust, 0, ol)};  // motor l
-    const float kT[1] = {P.use_rps ? AGX_QAT(B.motor_kT, 0, ol) : 1.0f};
-    const float tinc[1] = {B.motor_tau_inc ? AGX_QAT(B.motor_tau_inc, 0, ol) : P.tau_inc_uniform};
-    const float tdec[1] = {B.motor_tau_dec ? AGX_QAT(B.motor_tau_dec, 0, ol) : P.tau_dec_uniform};
-    const float a_in = actions_in[(size_t)i * 4 + l];
-    const float a_old = AGX_QAT(B.actions, 0, ol);
-    const float kp = B.gains ? AGX_QAT(B.gains, 0, ol3) : P.gains_uniform[0 + l3];
-    const float kv = B.gains ? AGX_QAT(B.gains, 3, ol3) : P.gains_uniform[3 + l3];
-    const float kr = B.gains ? AGX_QAT(B.gains, 6, ol3) : P.gains_uniform[6 + l3];
-    const float kw = B.gains ? AGX_QAT(B.gains, 9, ol3) : P.gains_uniform[9 + l3];
-    // what the task epilogue reads is requested HERE, with the state: behind the stores below the compiler cannot move a load up
-    // (the buffers may alias for all it knows), and a load issued there is a second memory round trip on the kernel's critical
-    // path -- one that also waits for every store in front of it (gfx9 counts loads and stores in the same vmcnt)
-    const int steps_in = B.sim_steps[i];
-    const float tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
-    const QuadConsts<4> C = load_quad_consts<4>(P, l, l3);
-
-    // ---- update_states + controller (position_control.py:20-51)
-    const float a = clamp_minmax(a_in, -10.0f, 10.0f);  // clip_actions
-    float sy_sp, cy_sp;  // of the yaw set-point (lanes 0, 1), out of the evaluation that serves the vehicle-frame quaternion
-    const QuadDerived d = update_states_quad(q, v, w, q4::bc<3>(a), sy_sp, cy_sp);
-    // compute_acceleration (velocity set-point 0): kp (sp - p) + kv (0 - v)
-    const float pe = a - p;
-    const float ve = 0.0f - v;
-    const float acc = kp * pe + kv * ve;
-    const float f = (acc - C.grav) * C.mass;
-    const float fz = quad_thrust_along_body_z(q, f, l);
-    const float qd = quad_desired_orientation_pos_vel_sc(f, sy_sp, cy_sp, l);
-    const float torque = quad_body_torque<true>(C, q, qd, d.wbody, 0.0f, kr, kw, l);
-
-    // ---- allocation + motor model + body wrench, rigid-body update
-    float fb, tb;
-    quad_allocate<4>(P, C, l == 2 ? fz : 0.0f, torque, u, kT, tinc, tdec, fb, tb);
-    if (B.body_force && l < 3) AGX_QAT(B.body_force, 0, ol) = fb;
-    quad_integrate(P, C, p, q, v, w, fb, tb, l);
-
-    // ---- stores: state, derived, motors, controller output, actions
-    if (l < 3) AGX_QAT(B.state, 0, ol) = p;
-    AGX_QAT(B.state, 3, ol) = q;
-    if (l < 3) {
-      AGX_QAT(B.state, 7, ol) = v;
-      AGX_QAT(B.state, 10, ol) = w;
-      AGX_QAT(B.derived, 0, ol) = d.euler;
-      AGX_QAT(B.derived, 7, ol) = d.vveh;
-      AGX_QAT(B.derived, 10, ol) = d.vbody;
-      AGX_QAT(B.derived, 13, ol) = d.wbody;
-    }
-    AGX_QAT(B.derived, 3, ol) = d.qveh;
-    AGX_QAT(B.motor_thrust, 0, ol) = u[0];
-    if (B.wrench_cmd) {
-      if (l < 3) {
-        AGX_QAT(B.wrench_cmd, 0, ol) = l == 2 ? fz : 0.0f;
-        AGX_QAT(B.wrench_cmd, 3, ol) = torque;
-      }
-    }
-    AGX_QAT(B.prev_actions, 0, ol) = a_old;  // RobotManagerIGE.pre_physics_step: prev <- cur, cur <- action
-    AGX_QAT(B.actions, 0, ol) = a_in;
-
-    // ---- EnvManager bookkeeping + the position task's reward / truncation / reset set (position_setpoint_task.py:245-282)
-    const int steps = steps_in + 1;
-    bool crashed = false, trunc = false;
-    float rew = 0.0f;
-    if (T.kind == AGX_TASK_POSITION) {
-      const float pe_t = q4::quat_apply(q4::conj(d.qveh), tgt - p);  // quat_apply_inverse
-      const float dist = q4::norm3(pe_t);
-      // 3 exp(-8 d^2) + 2 exp(-4 d^2): both exponentials in one evaluation (lanes 0 / 1)
-      const float ex = exp_cw((l == 0 ? -8.0f : -4.0f) * dist * dist);
-      const float pos_reward = 3.0f * q4::bc<0>(ex) + 2.0f * q4::bc<1>(ex);
-      const float dist_reward = (20.0f - dist) / 40.0f;
-      const float axis_z = l == 2 ? 1.0f : 0.0f;
-      const float up = q4::bc<2>(q4::quat_rotate(q, axis_z));  // quat_axis(q, 2).z
-      const float tilt = fabsf(1.0f - up);
-      const float spin = q4::norm3(d.wbody);
-      // 0.2 / (0.1 + tilt^2) = reciprocal * 0.2 (torch's scalar / tensor) and (1 / (1 + spin^2)) * 3: one division (lanes 0 / 1)
-      const float quo = (1.0f / (l == 0 ? 0.1f + tilt * tilt : 1.0f + spin * spin)) * (l == 0 ? 0.2f : 3.0f);
-      const float up_reward = q4::bc<0>(quo);
-      const float ang_reward = q4::bc<1>(quo);
-      float total = pos_reward + dist_reward + pos_reward * (up_reward + ang_reward);
-      total = 1.0f * total;
-      if (dist > 8.0f) crashed = true;
-      if (crashed) total = -20.0f;
-      rew = total;
-      trunc = steps > T.episode_len;
-      reset = (crashed && T.reset_on_collision) || trunc;
-    }
-    if (l == 0) {
-      B.sim_steps[i] = steps;
-      if (T.kind == AGX_TASK_POSITION) {
-        T.reward[i] = rew;
-        B.reset_mask[i] = reset ? 1 : 0;
-      }
-      B.crashes[i] = crashed ? 1 : 0;
-      B.truncations[i] = trunc ? 1 : 0;
-    }
-  }
-  if (T.kind != AGX_TASK_NONE && __ballot(reset) != 0ull && (tid & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
-  if (blockIdx.x == 0) push_wait_finish(B, push_peek);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2113,6 +2005,298 @@ __global__ void __launch_bounds__(64, 1) k_reset_masked_quad_obs_host_draws(AgxR
   reset_masked_quad_obs_body<true>(P, B, n, R, target, obs);
 }
 
+// ---- single-launch position steps: the proof record (include/aerial_gym_hip.h, AgxPositionStepPlan) ---------------------------
+// Every wave of a position-step launch of a plan leaves a slot about the END of its step, double-buffered by the step's parity
+// (the folding workgroup of launch u reads bank (u - 1) & 1 while the waves of launch u write bank u & 1):
+//   [0] tag = step_counter + 1 (31 bits)   [1] bit 0: some env of the wave reset, bit 1: the launch was AGX_STEP_ANY
+//   [2] horizon: bit k = a witness env truncates in step t + k   [3] max sim_steps   [4] max dist bits   [5] max |v| bits
+// dist and |v| are >= 0, so their bit patterns order like the values; NaN maps to 0x7FC00000, above every finite value and inf.
+AGX_DEV unsigned proof_key(float x) { return x >= 0.0f ? __float_as_uint(x) : 0x7FC00000u; }
+
+// env i is a witness for step t + k (k = episode_len - sim_steps + 1: it truncates then) if it did not reset in step t and cannot
+// reset before: k = 1, or crashes do not reset, or it cannot get 8 m from its target in k - 1 steps, where m steps take it at
+// most m dt min(v_max, |v| + m dv) (agx_step_proof_travel, per_env, margins included).  NaN distances or speeds: never witnesses.
+// (host and device: agx_step_proof_witness_bit exports it to the CPU tests)
+__host__ __device__ inline unsigned proof_witness_bit(int episode_len, int reset_on_collision, int steps, float dist, float speed, float dt,
+                                                      float vmax, float dv) {
+  const int k = episode_len - steps + 1;
+  if (k < 1 || k > AGX_PROOF_HORIZON || !(dist == dist) || !(speed == speed)) return 0u;
+  bool w = k == 1 || !reset_on_collision;
+  if (!w) {
+    const float m = (float)(k - 1);
+    const float travel = m * dt * fminf(vmax, speed + m * dv);
+    w = dist + (travel * 1.01f + 1.0e-3f) < 8.0f;
+  }
+  return w ? (1u << k) : 0u;
+}
+
+AGX_DEV void proof_store_slot(const AgxTaskArgs &T, const AgxEnvBuffers &B, int wb, int nb, bool reset, unsigned horizon, int steps,
+                              float dist, float speed) {
+  unsigned ar = reset ? 1u : 0u, hz = horizon, ms = (unsigned)max(steps, 0), db = proof_key(dist), vb = proof_key(speed);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    ar |= (unsigned)__shfl_xor((int)ar, off);
+    hz |= (unsigned)__shfl_xor((int)hz, off);
+    ms = max(ms, (unsigned)__shfl_xor((int)ms, off));
+    db = max(db, (unsigned)__shfl_xor((int)db, off));
+    vb = max(vb, (unsigned)__shfl_xor((int)vb, off));
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    uint4 *slot = reinterpret_cast<uint4 *>(T.proof_slots + ((size_t)(B.step_counter & 1) * nb + wb) * AGX_PROOF_SLOT_WORDS);
+    slot[0] = make_uint4(((unsigned)B.step_counter + 1u) & 0x7FFFFFFFu, ar | (T.proof_mode == AGX_STEP_ANY ? 2u : 0u), hz, ms);
+    slot[1] = make_uint4(db, vb, 0u, 0u);
+  }
+}
+
+// workgroup 0 of a launch with slots: fold the `nb` slots of the launch before (complete: kernel boundary) and publish them to
+// the host record -- begin tag, payload, end tag, each acknowledged before the next is stored (system-scope write-through stores
+// to mapped host memory: acknowledged = visible to the host).  An AGX_STEP_ANY launch in which no env reset is a broken proof.
+AGX_DEV void proof_fold_publish(const AgxTaskArgs &T, const AgxEnvBuffers &B, int nb) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t *bank = T.proof_slots + (size_t)((B.step_counter & 1) ^ 1) * nb * AGX_PROOF_SLOT_WORDS;
+  unsigned t_and = 0x7FFFFFFFu, t_or = 0u, fl = 0u, hz = 0u, ms = 0u, db = 0u, vb = 0u;
+  for (int b = lane; b < nb; b += 64) {
+    const uint4 s0 = reinterpret_cast<const uint4 *>(bank + (size_t)b * AGX_PROOF_SLOT_WORDS)[0];
+    const uint4 s1 = reinterpret_cast<const uint4 *>(bank + (size_t)b * AGX_PROOF_SLOT_WORDS)[1];
+    t_and &= s0.x; t_or |= s0.x; fl |= s0.y; hz |= s0.z;
+    ms = max(ms, s0.w); db = max(db, s1.x); vb = max(vb, s1.y);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    t_and &= (unsigned)__shfl_xor((int)t_and, off);
+    t_or |= (unsigned)__shfl_xor((int)t_or, off);
+    fl |= (unsigned)__shfl_xor((int)fl, off);
+    hz |= (unsigned)__shfl_xor((int)hz, off);
+    ms = max(ms, (unsigned)__shfl_xor((int)ms, off));
+    db = max(db, (unsigned)__shfl_xor((int)db, off));
+    vb = max(vb, (unsigned)__shfl_xor((int)vb, off));
+  }
+  if (lane != 0) return;
+  const unsigned tag = t_and == t_or ? t_or : 0u;  // every slot written by the same launch, else: not a record
+  if (tag != 0u && (fl & 2u) && !(fl & 1u)) atomicAdd(T.proof_violation, 1u);
+  uint32_t *h = T.proof_record;
+  __hip_atomic_store(h + 7, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (compiler: keep the order)
+  __builtin_amdgcn_s_waitcnt(0);                          // (hardware: acknowledged)
+  __hip_atomic_store(h + 1, hz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(h + 2, ms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(h + 3, db, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(h + 4, vb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(h + 5, fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_s_waitcnt(0);
+  __hip_atomic_store(h + 0, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One env step of the plain quadrotor position task, four lanes per env.  MODE:
+//   AGX_STEP_TWO   the first of the two launches (k_env_step_quad_position): step, derived tensors of the pre-step state,
+//                  task epilogue; k_reset_masked_quad_obs follows
+//   AGX_STEP_ANY   the whole step when some env certainly resets: as TWO without the (dead) pre-step derived stores, then
+//                  what k_reset_masked_quad_obs does with its flag set -- the reset of the env's own flagged envs, the refresh
+//                  of every env from its post-step / post-reset state, the observation
+//   AGX_STEP_NONE  the whole step when no env can reset: as TWO, then the observation from the pre-step derived tensors (what
+//                  k_reset_masked_quad_obs reads back with its flag clear)
+// Same IEEE operations in the same order in every mode (bit-identical); the fused modes write no address from two lanes (the
+// sub-step's state, thrust and sim_steps stores are skipped for an env that reset_env rewrites) and carry no step exchange.
+template <int MODE>
+AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const float *__restrict__ actions_in,
+                                const AgxTaskArgs &T, const AgxResetArgs &R, float *__restrict__ obs) {
+  constexpr bool FUSED = MODE != AGX_STEP_TWO;
+  const int tid = threadIdx.x;
+  const bool proof = T.proof_slots != nullptr;
+  if (proof && blockIdx.x == 0) {  // the extra workgroup of a launch with slots: no envs, only the host record
+    proof_fold_publish(T, B, (int)gridDim.x - 1);
+    return;
+  }
+  const int wb = (int)blockIdx.x - (proof ? 1 : 0);  // env block
+  const int l = tid & 3, l3 = l < 3 ? l : 2;  // component of a 4-vector / of a 3-vector (lane 3 repeats z: don't care)
+  const int i = wb * 16 + (tid >> 2);  // env
+  const unsigned ol = ((unsigned)l * (unsigned)n + (unsigned)i) * 4u, ol3 = ((unsigned)l3 * (unsigned)n + (unsigned)i) * 4u;  // AGX_QAT
+  const bool valid = i < n;
+  bool reset = false;
+  if (FUSED && wb == 0 && tid == 0) B.reset_flag[B.flag_parity ^ 1] = 0;  // (what the second launch does first)
+  if (!FUSED && wb == 0) push_publish_previous(B);  // peer push: the previous step's rows have landed everywhere
+  const uint32_t push_peek = (!FUSED && wb == 0) ? push_wait_peek(B) : 0u;  // ... and this step's slot: looked at when the kernel is done
+  float p = 0.0f, q = 0.0f, v = 0.0f, w = 0.0f, tgt = 0.0f, vbody = 0.0f, wbody = 0.0f;
+  int steps = 0, ep = 0;
+  float proof_dist = 0.0f, proof_speed = 0.0f;
+  unsigned horizon = 0u;
+  if (valid) {
+    // ---- loads: one instruction per vector
+    p = AGX_QAT(B.state, 0, ol3); q = AGX_QAT(B.state, 3, ol); v = AGX_QAT(B.state, 7, ol3); w = AGX_QAT(B.state, 10, ol3);
+    float u[1] = {AGX_QAT(B.motor_thrust, 0, ol)};  // motor l
+    const float kT[1] = {P.use_rps ? AGX_QAT(B.motor_kT, 0, ol) : 1.0f};
+    const float tinc[1] = {B.motor_tau_inc ? AGX_QAT(B.motor_tau_inc, 0, ol) : P.tau_inc_uniform};
+    const float tdec[1] = {B.motor_tau_dec ? AGX_QAT(B.motor_tau_dec, 0, ol) : P.tau_dec_uniform};
+    const float a_in = actions_in[(size_t)i * 4 + l];
+    const float a_old = AGX_QAT(B.actions, 0, ol);
+    const float kp = B.gains ? AGX_QAT(B.gains, 0, ol3) : P.gains_uniform[0 + l3];
+    const float kv = B.gains ? AGX_QAT(B.gains, 3, ol3) : P.gains_uniform[3 + l3];
+    const float kr = B.gains ? AGX_QAT(B.gains, 6, ol3) : P.gains_uniform[6 + l3];
+    const float kw = B.gains ? AGX_QAT(B.gains, 9, ol3) : P.gains_uniform[9 + l3];
+    // what the task epilogue reads is requested HERE, with the state: behind the stores below the compiler cannot move a load up
+    // (the buffers may alias for all it knows), and a load issued there is a second memory round trip on the kernel's critical
+    // path -- one that also waits for every store in front of it (gfx9 counts loads and stores in the same vmcnt)
+    const int steps_in = B.sim_steps[i];
+    tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
+    if (MODE == AGX_STEP_ANY && B.episode_count) ep = B.episode_count[i];  // (the reset's draws are keyed by it)
+    const QuadConsts<4> C = load_quad_consts<4>(P, l, l3);
+
+    // ---- update_states + controller (position_control.py:20-51)
+    const float a = clamp_minmax(a_in, -10.0f, 10.0f);  // clip_actions
+    float sy_sp, cy_sp;  // of the yaw set-point (lanes 0, 1), out of the evaluation that serves the vehicle-frame quaternion
+    const QuadDerived d = update_states_quad(q, v, w, q4::bc<3>(a), sy_sp, cy_sp);
+    // compute_acceleration (velocity set-point 0): kp (sp - p) + kv (0 - v)
+    const float pe = a - p;
+    const float ve = 0.0f - v;
+    const float acc = kp * pe + kv * ve;
+    const float f = (acc - C.grav) * C.mass;
+    const float fz = quad_thrust_along_body_z(q, f, l);
+    const float qd = quad_desired_orientation_pos_vel_sc(f, sy_sp, cy_sp, l);
+    const float torque = quad_body_torque<true>(C, q, qd, d.wbody, 0.0f, kr, kw, l);
+
+    // ---- allocation + motor model + body wrench, rigid-body update
+    float fb, tb;
+    quad_allocate<4>(P, C, l == 2 ? fz : 0.0f, torque, u, kT, tinc, tdec, fb, tb);
+    if (B.body_force && l < 3) AGX_QAT(B.body_force, 0, ol) = fb;
+    quad_integrate(P, C, p, q, v, w, fb, tb, l);
+
+    // ---- EnvManager bookkeeping + the position task's reward / truncation / reset set (position_setpoint_task.py:245-282)
+    steps = steps_in + 1;
+    bool crashed = false, trunc = false;
+    float rew = 0.0f;
+    if (T.kind == AGX_TASK_POSITION) {
+      const float pe_t = q4::quat_apply(q4::conj(d.qveh), tgt - p);  // quat_apply_inverse
+      const float dist = q4::norm3(pe_t);
+      // 3 exp(-8 d^2) + 2 exp(-4 d^2): both exponentials in one evaluation (lanes 0 / 1)
+      const float ex = exp_cw((l == 0 ? -8.0f : -4.0f) * dist * dist);
+      const float pos_reward = 3.0f * q4::bc<0>(ex) + 2.0f * q4::bc<1>(ex);
+      const float dist_reward = (20.0f - dist) / 40.0f;
+      const float axis_z = l == 2 ? 1.0f : 0.0f;
+      const float up = q4::bc<2>(q4::quat_rotate(q, axis_z));  // quat_axis(q, 2).z
+      const float tilt = fabsf(1.0f - up);
+      const float spin = q4::norm3(d.wbody);
+      // 0.2 / (0.1 + tilt^2) = reciprocal * 0.2 (torch's scalar / tensor) and (1 / (1 + spin^2)) * 3: one division (lanes 0 / 1)
+      const float quo = (1.0f / (l == 0 ? 0.1f + tilt * tilt : 1.0f + spin * spin)) * (l == 0 ? 0.2f : 3.0f);
+      const float up_reward = q4::bc<0>(quo);
+      const float ang_reward = q4::bc<1>(quo);
+      float total = pos_reward + dist_reward + pos_reward * (up_reward + ang_reward);
+      total = 1.0f * total;
+      if (dist > 8.0f) crashed = true;
+      if (crashed) total = -20.0f;
+      rew = total;
+      trunc = steps > T.episode_len;
+      reset = (crashed && T.reset_on_collision) || trunc;
+      proof_dist = dist;
+    }
+    if (proof) {
+      proof_speed = q4::norm3(v);  // the post-step linear speed
+      if (l == 0 && !reset && T.kind == AGX_TASK_POSITION) horizon = proof_witness_bit(T.episode_len, T.reset_on_collision, steps, proof_dist, proof_speed, P.dt, P.max_linear_velocity,
+                                    T.proof_dv);
+    }
+
+    // ---- stores: state, derived, motors, controller output, actions (reset_env rewrites state, thrust and sim_steps of an env
+    // that resets in a fused launch: it alone stores them then)
+    const bool own = MODE != AGX_STEP_ANY || !reset;
+    if (own) {
+      if (l < 3) AGX_QAT(B.state, 0, ol) = p;
+      AGX_QAT(B.state, 3, ol) = q;
+      if (l < 3) {
+        AGX_QAT(B.state, 7, ol) = v;
+        AGX_QAT(B.state, 10, ol) = w;
+      }
+      AGX_QAT(B.motor_thrust, 0, ol) = u[0];
+    }
+    if (MODE != AGX_STEP_ANY) {  // (ANY: the refresh below overwrites them)
+      if (l < 3) {
+        AGX_QAT(B.derived, 0, ol) = d.euler;
+        AGX_QAT(B.derived, 7, ol) = d.vveh;
+        AGX_QAT(B.derived, 10, ol) = d.vbody;
+        AGX_QAT(B.derived, 13, ol) = d.wbody;
+      }
+      AGX_QAT(B.derived, 3, ol) = d.qveh;
+    }
+    vbody = d.vbody;
+    wbody = d.wbody;
+    if (B.wrench_cmd) {
+      if (l < 3) {
+        AGX_QAT(B.wrench_cmd, 0, ol) = l == 2 ? fz : 0.0f;
+        AGX_QAT(B.wrench_cmd, 3, ol) = torque;
+      }
+    }
+    AGX_QAT(B.prev_actions, 0, ol) = a_old;  // RobotManagerIGE.pre_physics_step: prev <- cur, cur <- action
+    AGX_QAT(B.actions, 0, ol) = a_in;
+    if (l == 0) {
+      if (own) B.sim_steps[i] = steps;
+      if (T.kind == AGX_TASK_POSITION) {
+        T.reward[i] = rew;
+        B.reset_mask[i] = reset ? 1 : 0;
+      }
+      B.crashes[i] = crashed ? 1 : 0;
+      B.truncations[i] = trunc ? 1 : 0;
+    }
+  }
+  const bool some = __ballot(reset) != 0ull;
+  if (T.kind != AGX_TASK_NONE && some && (tid & 63) == 0) {
+    atomicOr(B.reset_flag + B.flag_parity, 1);
+    if (MODE == AGX_STEP_NONE) atomicAdd(T.proof_violation, 1u);  // cannot happen (the host proved it): tests watch this word
+  }
+  if (proof) proof_store_slot(T, B, wb, (int)gridDim.x - 1, reset, horizon, steps, proof_dist, proof_speed);
+  if (!FUSED) {
+    if (wb == 0) push_wait_finish(B, push_peek);
+    return;
+  }
+  if (MODE == AGX_STEP_ANY) {
+    // k_reset_masked_quad_obs with its flag set (reset_masked_quad_obs_body<false>): the env's own reset ...
+    const bool mine = reset;
+    const bool lead = mine && l == 0;
+    ResetDraws<4> D{};
+    wave_reset_draws<4>(R, B.env_index_base + i, ep, lead, D);  // draws are keyed by the GLOBAL env index
+    if (some) {
+      EnvState s{};
+      if (lead) s = reset_env<4>(P, B, n, R, i, ep, D);
+      // the quad takes the new state over from its first lane
+      const float npv = q4::by_lane(l3, q4::bc<0>(s.p.x), q4::bc<0>(s.p.y), q4::bc<0>(s.p.z));
+      const float nq = q4::by_lane(l, q4::bc<0>(s.q.x), q4::bc<0>(s.q.y), q4::bc<0>(s.q.z), q4::bc<0>(s.q.w));
+      const float nv = q4::by_lane(l3, q4::bc<0>(s.v.x), q4::bc<0>(s.v.y), q4::bc<0>(s.v.z));
+      const float nw = q4::by_lane(l3, q4::bc<0>(s.w.x), q4::bc<0>(s.w.y), q4::bc<0>(s.w.z));
+      p = mine ? npv : p; q = mine ? nq : q; v = mine ? nv : v; w = mine ? nw : w;
+    }
+    // ... and BaseMultirotor.reset_idx's un-indexed update_states(): every env is refreshed
+    const QuadDerived d2 = update_states_quad(q, v, w);
+    if (valid) {
+      if (l < 3) {
+        AGX_QAT(B.derived, 0, ol) = d2.euler;
+        AGX_QAT(B.derived, 7, ol) = d2.vveh;
+        AGX_QAT(B.derived, 10, ol) = d2.vbody;
+        AGX_QAT(B.derived, 13, ol) = d2.wbody;
+      }
+      AGX_QAT(B.derived, 3, ol) = d2.qveh;
+    }
+    vbody = d2.vbody;
+    wbody = d2.wbody;
+  }
+  if (valid) {  // position_setpoint_task.py:194-203: target - p | q | v_body | w_body
+    float *o = obs + (size_t)i * 13;
+    const float e = tgt - p;
+    if (l < 3) { o[l] = e; o[7 + l] = vbody; o[10 + l] = wbody; }
+    o[3 + l] = q;
+  }
+}
+
+__global__ void __launch_bounds__(64, 1)
+    k_env_step_quad_position(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, AgxTaskArgs T) {
+  position_step_quad<AGX_STEP_TWO>(P, B, n, actions_in, T, AgxResetArgs{}, nullptr);
+}
+
+// The whole position step as ONE launch (agx_position_task_step, when the host record proves the outcome of the batch-wide reset
+// OR): AGX_STEP_ANY or AGX_STEP_NONE, always with the proof slots and the folding workgroup 0.
+template <int MODE>
+__global__ void __launch_bounds__(64, 1) k_position_step_fused(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in,
+                                                               AgxTaskArgs T, AgxResetArgs R, float *__restrict__ obs) {
+  position_step_quad<MODE>(P, B, n, actions_in, T, R, obs);
+}
+
 // AssetManager.reset_idx (asset_manager.py:51-71) + the half-obstacle resample (env_manager.py:283-295)
 __global__ void __launch_bounds__(256) k_reset_assets(AgxEnvBuffers B, int n, int K, AgxResetArgs R, const float *__restrict__ u1,
                                                        const float *__restrict__ u2, const float *__restrict__ u_sel,
@@ -2243,10 +2427,12 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
   const int block = pick_block(n);
   const size_t lds = B->boxes ? (size_t)k * 3 * block * sizeof(float) : 0;
   if (k == 1 && block == 64 && P->num_motors == 4 && P->controller == AGX_CTRL_POSITION && quad_kernel_usable(P, B, &T)) {
-    hipLaunchKernelGGL(k_env_step_quad_position, dim3(blocks_for(n, 16)), dim3(64), 0, (hipStream_t)stream, *P, *B, n, actions_in,
-                       T);
+    // (with proof slots: one more workgroup, the first, folds the previous launch's slots into the host record)
+    hipLaunchKernelGGL(k_env_step_quad_position, dim3(blocks_for(n, 16) + (T.proof_slots ? 1 : 0)), dim3(64), 0, (hipStream_t)stream, *P,
+                       *B, n, actions_in, T);
     return check_launch("agx_env_step");
   }
+  AGX_REQUIRE(!T.proof_slots && T.proof_mode == AGX_STEP_TWO, "AgxTaskArgs.proof_*: the four-lanes-per-env position kernel only");
   if (quad_loop_kernel_usable(P, B, n, k)) {
     const size_t lds4 = B->boxes ? (size_t)k * 3 * 16 * sizeof(float) : 0;
     if (P->num_motors == 8 && P->controller == AGX_CTRL_POSITION) {
@@ -2489,12 +2675,186 @@ extern "C" int agx_push_advance(AgxEnvBuffers *b) {
   return AGX_OK;
 }
 
-extern "C" int agx_position_task_step(const AgxPositionStepPlan *plan, const float *actions_in, void *stream) {
+// ---- single-launch position steps: the host side (include/aerial_gym_hip.h, AgxPositionStepPlan) -------------------------------
+extern "C" float agx_step_proof_dv(const AgxRobotParams *P) {
+  if (!P || !(P->mass > 0.0f)) return INFINITY;
+  const int M = P->num_motors;
+  const float *wmap = P->root_link_mode != 0 ? P->alloc : P->wrench_map;  // (the map the kernels use: force rows 0..2 of [6][M])
+  float col = 0.0f;  // sum over the motors of |force per unit thrust|: the body force is at most that times max |thrust|
+  for (int j = 0; j < M; ++j) col += sqrtf(wmap[j] * wmap[j] + wmap[M + j] * wmap[M + j] + wmap[2 * M + j] * wmap[2 * M + j]);
+  const float g = sqrtf(P->gravity[0] * P->gravity[0] + P->gravity[1] * P->gravity[1] + P->gravity[2] * P->gravity[2]);
+  return (col * fmaxf(fabsf(P->max_thrust), fabsf(P->min_thrust)) / P->mass + g) * P->dt * 1.1f;
+}
+
+extern "C" float agx_step_proof_travel(int m, float speed, float dt, float vmax, float dv, int per_env) {
+  if (m <= 0) return 0.0f;
+  float travel = 0.0f;
+  if (per_env) {
+    travel = (float)m * dt * fminf(vmax, speed + (float)m * dv);  // (the device's proof_witness_bit, same expression)
+  } else {
+    float v = speed;
+    for (int k = 0; k < m; ++k) {
+      v = fminf(v + dv, vmax);
+      travel += v * dt;
+    }
+  }
+  return travel * 1.01f + 1.0e-3f;
+}
+
+extern "C" uint32_t agx_step_proof_witness_bit(int episode_len, int reset_on_collision, int steps, float dist, float speed, float dt,
+                                               float max_linear_velocity, float dv) {
+  return proof_witness_bit(episode_len, reset_on_collision, steps, dist, speed, dt, max_linear_velocity, dv);
+}
+
+extern "C" int agx_step_proof_decide(const uint32_t *record, const AgxStepProofQuery *q, int32_t *reason) {
+  int32_t why = AGX_PROOF_PROVED;
+  int mode = AGX_STEP_TWO;
+  if (!record || !q) {
+    why = AGX_PROOF_OFF;
+  } else {
+    // seqlock read: the writer stores [7] begin, the payload, [0] end, each acknowledged before the next
+    volatile const uint32_t *h = record;
+    const uint32_t end = h[0];
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const uint32_t hz = h[1], ms = h[2], db = h[3], vb = h[4], fl = h[5];
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const uint32_t begin = h[7];
+    const uint32_t k = (q->now_tag - end) & 0x7FFFFFFFu;  // steps from the recorded step to this one
+    float dist, speed;
+    memcpy(&dist, &db, 4);
+    memcpy(&speed, &vb, 4);
+    if (end != begin) why = AGX_PROOF_TORN;
+    else if (end == 0u) why = AGX_PROOF_NO_RECORD;
+    else if (((end - q->min_tag) & 0x7FFFFFFFu) >= 0x40000000u) why = AGX_PROOF_VOID;  // recorded before the host's last interference
+    else if (k == 0u || k > 64u) why = AGX_PROOF_TAG;
+    else if (k <= AGX_PROOF_HORIZON && ((hz >> k) & 1u)) mode = AGX_STEP_ANY;  // a witness truncates in this step
+    else if (fl & 1u) why = AGX_PROOF_RESET_NO_WITNESS;  // (the recorded maxima do not describe the envs that reset)
+    else if ((int64_t)ms + (int64_t)k > (int64_t)q->episode_len) why = AGX_PROOF_MAY_TRUNCATE;
+    else if (q->reset_on_collision && (!(speed == speed) ||  // (fminf would hide a NaN speed; a NaN distance fails the compare)
+                                       !(dist + agx_step_proof_travel((int)k, speed, q->dt, q->max_linear_velocity, q->dv, 0) < 8.0f)))
+      why = AGX_PROOF_MAY_CRASH;
+    else mode = AGX_STEP_NONE;
+  }
+  if (reason) *reason = why;
+  return mode;
+}
+
+extern "C" int agx_host_record_alloc(size_t bytes, void **out) {
+  AGX_REQUIRE(out && bytes > 0 && bytes <= (1u << 20), "bad arguments");
+  void *p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "hipHostMalloc(%zu, mapped | coherent): %s", bytes, hipGetErrorString(e));
+  memset(p, 0, bytes);
+  *out = p;
+  return AGX_OK;
+}
+
+extern "C" int agx_host_record_free(void *p) {
+  if (p) (void)hipHostFree(p);
+  return AGX_OK;
+}
+
+// Which form this step takes: the two launches without slots (not covered), the two launches with slots, or one launch.
+static int position_step_mode(AgxPositionStepPlan *plan, const AgxTaskArgs &T, hipStream_t stream, bool *slots, int32_t *reason) {
+  *slots = false;
+  const AgxEnvBuffers *B = plan->buf;
+  const AgxRobotParams *P = plan->params;
+  if (!option_single_launch_step() || !plan->proof_slots || !plan->proof_record || !plan->proof_violation) {
+    *reason = AGX_PROOF_OFF;
+    return AGX_STEP_TWO;
+  }
+  const bool covered = plan->k_substeps == 1 && pick_block(plan->num_envs) == 64 && P->num_motors == 4 &&
+                       P->controller == AGX_CTRL_POSITION && T.kind == AGX_TASK_POSITION && quad_kernel_usable(P, B, &T) &&
+                       plan->reset->u_state == nullptr && B->episode_count && !B->step_rows[0] && !B->step_rows[1] &&
+                       !B->step_signal && B->push_world <= 0 && !B->step_counter_dev && plan->obs && plan->target == T.target;
+  if (!covered) {
+    *reason = AGX_PROOF_NOT_COVERED;
+    return AGX_STEP_TWO;
+  }
+  if (!plan->captured) {  // a step captured into a graph is replayed whatever the state is then, and the host does not see it
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) plan->captured = 1;
+  }
+  if (plan->captured) {
+    *reason = AGX_PROOF_CAPTURE;
+    return AGX_STEP_TWO;
+  }
+  *slots = true;
+  const int max_lag = plan->max_lag > 0 ? plan->max_lag : 8;
+  AgxStepProofQuery Q{};
+  Q.now_tag = ((uint32_t)B->step_counter + 1u) & 0x7FFFFFFFu;
+  Q.min_tag = plan->proof_min_tag;
+  Q.episode_len = T.episode_len;
+  Q.reset_on_collision = T.reset_on_collision;
+  Q.dt = P->dt;
+  Q.max_linear_velocity = P->max_linear_velocity;
+  Q.dv = T.proof_dv;
+  // Bounded run-ahead: a host that enqueues faster than the device executes gets ahead by the depth of the queue, and a record
+  // from far back proves little.  More than max_lag steps ahead of the newest record, spin on it (no HIP call, at most 2 ms).
+  // Only when the record can catch up: the last max_lag + 1 launches of this plan wrote slots.
+  if (plan->slot_run > max_lag) {
+    volatile const uint32_t *h = plan->proof_record;
+    uint32_t k = (Q.now_tag - h[0]) & 0x7FFFFFFFu;
+    if (h[0] != 0u && k > (uint32_t)max_lag && k <= 64u) {
+      const auto t0 = std::chrono::steady_clock::now();
+      for (unsigned spin = 1;; ++spin) {
+        k = (Q.now_tag - h[0]) & 0x7FFFFFFFu;
+        if (k <= (uint32_t)max_lag || k > 64u) break;
+        __builtin_ia32_pause();
+        if ((spin & 255u) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) {
+          *reason = AGX_PROOF_LAG;
+          return AGX_STEP_TWO;
+        }
+      }
+    }
+  }
+  return agx_step_proof_decide(plan->proof_record, &Q, reason);
+}
+
+extern "C" int agx_position_task_step(AgxPositionStepPlan *plan, const float *actions_in, void *stream) {
   AGX_REQUIRE(plan && plan->params && plan->buf && plan->task && plan->reset, "null plan member");
+  AGX_REQUIRE(plan->max_lag == 0 || (plan->max_lag >= 2 && plan->max_lag < AGX_PROOF_HORIZON), "max_lag %d outside 2 .. %d (0: 8)",
+              plan->max_lag, AGX_PROOF_HORIZON - 1);
   plan->buf->flag_parity ^= 1;  // new env step: the flag the previous step's reset kernel cleared
   if (plan->buf->push_world > 0)
     if (int e = agx_push_advance(plan->buf)) return e;
-  if (int e = agx_env_step(plan->params, plan->buf, plan->num_envs, actions_in, plan->k_substeps, plan->task, stream)) return e;
+  AgxTaskArgs T = *plan->task;
+  T.proof_slots = nullptr;
+  T.proof_record = nullptr;
+  T.proof_violation = nullptr;
+  T.proof_mode = AGX_STEP_TWO;
+  T.proof_dv = agx_step_proof_dv(plan->params);
+  bool slots = false;
+  int32_t why = AGX_PROOF_OFF;
+  const int mode = position_step_mode(plan, T, (hipStream_t)stream, &slots, &why);
+  plan->last_mode = mode;
+  plan->last_reason = why;
+  plan->mode_count[mode] += 1;
+  plan->reason_count[why] += 1;
+  plan->slot_run = slots ? plan->slot_run + 1 : 0;
+  if (slots) {
+    T.proof_slots = plan->proof_slots;
+    T.proof_record = plan->proof_record;
+    T.proof_violation = plan->proof_violation;
+    T.proof_mode = mode;
+  }
+  if (mode != AGX_STEP_TWO) {
+    const AgxEnvBuffers *B = plan->buf;
+    const int n = plan->num_envs;
+    if (int e = check_reset(plan->params, B, n, plan->reset)) return e;
+    AGX_REQUIRE(actions_in && B->state && B->derived && B->actions && B->prev_actions && B->motor_thrust && B->crashes && B->truncations &&
+                    B->sim_steps && T.target && T.reward,
+                "null buffer");
+    const dim3 grid(blocks_for(n, 16) + 1);
+    if (mode == AGX_STEP_ANY)
+      hipLaunchKernelGGL(k_position_step_fused<AGX_STEP_ANY>, grid, dim3(64), 0, (hipStream_t)stream, *plan->params, *B, n, actions_in, T,
+                         *plan->reset, plan->obs);
+    else
+      hipLaunchKernelGGL(k_position_step_fused<AGX_STEP_NONE>, grid, dim3(64), 0, (hipStream_t)stream, *plan->params, *B, n, actions_in, T,
+                         *plan->reset, plan->obs);
+    return check_launch("agx_position_task_step");
+  }
+  if (int e = agx_env_step(plan->params, plan->buf, plan->num_envs, actions_in, plan->k_substeps, &T, stream)) return e;
   // peer push: the env-step kernel has waited (one wave) until the slot of this step's rows was vacated; the observation
   // kernel behind it need not look again
   const uint32_t wait_seq = plan->buf->push_wait_seq;

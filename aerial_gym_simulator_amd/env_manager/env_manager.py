@@ -320,9 +320,12 @@ class EnvManager(BaseManager):
             s = self._stream_cache = _lib.current_stream(self.device)
         return s
 
+    _calls = 0  # public calls so far (reset, reset_idx, step, render ...): a task's single-launch proof is void behind one
+
     def _new_call(self):
         self._stream_cache = None
         self._derived_stale = True
+        self._calls += 1
 
     # ---- lean step (args={"lean_step": True}): AGX_LAUNCH_LEAN for batches far above 65 536 envs, where bytes matter ------
     LEAN_MIN_ENVS = 65537
@@ -776,6 +779,7 @@ class EnvManager(BaseManager):
 
     @roctx.ranged("EnvManager.render")
     def render(self, render_components="sensors"):
+        self._calls += 1
         if render_components == "sensors":
             self.render_sensors()
 

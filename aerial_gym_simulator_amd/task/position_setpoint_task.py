@@ -56,6 +56,7 @@ class PositionSetpointTask(BaseTask):
         }
         self.infos = {}
         self._plan = None
+        self._proof_watch = self._proof_record = None
         self._fuse_with_env()
 
     def _fuse_with_env(self):
@@ -99,6 +100,9 @@ class PositionSetpointTask(BaseTask):
             self.task_obs["rewards"] = self.rewards
             self.task_obs["terminations"] = self.terminations
             self.task_obs["truncations"] = self.truncations
+            self._proof_watch = None
+            if not env.strict_rng:
+                self._enable_single_launch(plan)
             if env.strict_rng:
                 # reference-faithful RNG consumption, one host call per step: the two launches above with, between them, the
                 # reset flag published into a mapped host word the call spins on (no stream synchronisation) and -- only on a
@@ -123,6 +127,50 @@ class PositionSetpointTask(BaseTask):
                 self._strict_fn = env._lib.agx_position_task_step_strict
                 self._plan_fn = self._strict_step
 
+    def _enable_single_launch(self, plan):
+        """Single-launch steps (include/aerial_gym_hip.h, AgxPositionStepPlan.proof_*; on unless args={"single_launch_step":
+        False}): the kernels leave a record of each step's end in mapped host memory, and agx_position_task_step issues a step
+        whose reset outcome it proves from that record as ONE launch.  The proof is about what the KERNELS did: whenever the host
+        may have changed what it rests on -- the state, target, sim_steps or motor-thrust tensors written through torch (their
+        version counters move), any other public call on the env, a new episode length -- the records up to now are void
+        (`proof_min_tag`, set in step())."""
+        import ctypes as C
+
+        env = self.sim_env
+        if not bool(env.env_args.get("single_launch_step", True)) or env.num_envs > 65536 or env._params.num_motors != 4:
+            return
+        nb = (env.num_envs + 15) // 16
+        self._proof_slots = torch.zeros(2 * nb * _lib.PROOF_SLOT_WORDS, dtype=torch.int32, device=self.device)
+        self._proof_violation = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._free_proof_record()
+        rec = C.c_void_p()
+        _lib.check(env._lib.agx_host_record_alloc(_lib.PROOF_RECORD_WORDS * 4, C.byref(rec)), "agx_host_record_alloc")
+        self._proof_record = rec
+        plan.proof_slots, plan.proof_violation = _lib.dptr(self._proof_slots), _lib.dptr(self._proof_violation)
+        plan.proof_record = rec.value
+        plan.proof_min_tag = (env.step_counter + 1) & 0x7FFFFFFF
+        plan.max_lag = int(env.env_args.get("single_launch_max_lag", 8))
+        g = env.global_tensor_dict
+        self._proof_watch = (g["robot_state_soa"], self.target_soa, g["sim_steps"],
+                             env.robot_manager.robot.control_allocator.motor_model.thrust_soa)
+        self._proof_versions = None
+        self._proof_calls = -1
+
+    def _free_proof_record(self):
+        if self._proof_record is not None:
+            self.sim_env._lib.agx_host_record_free(self._proof_record)
+            self._proof_record = None
+
+    def single_launch_stats(self):
+        """How the fast path's steps ran: counts per mode (two launches, ONE launch with some env certainly resetting, ONE
+        launch with none resetting) and per reason (AGX_PROOF_*), and the device's violation word (reads it: synchronises)."""
+        p = self._plan
+        if p is None:
+            return None
+        return {"modes": dict(zip(_lib.STEP_MODES, (int(x) for x in p.mode_count))),
+                "reasons": dict(zip(_lib.PROOF_REASONS, (int(x) for x in p.reason_count))),
+                "violations": int(self._proof_violation.item()) if self._proof_watch is not None else 0}
+
     def _strict_step(self, plan_ref, actions_ptr, stream):
         """agx_position_task_step in the strict mode (same signature): generator state in, offset out"""
         sp, gen = self._strict, self._strict_gen
@@ -137,6 +185,10 @@ class PositionSetpointTask(BaseTask):
         if getattr(self, "_strict_word", None) is not None:
             self.sim_env._lib.agx_host_word_destroy(self._strict_word)
             self._strict_word = None
+        self._proof_watch = None
+        if self._plan is not None:
+            self._plan.proof_slots = self._plan.proof_record = self._plan.proof_violation = None
+        self._free_proof_record()
         self.sim_env.delete_env()
 
     def reset(self):
@@ -170,6 +222,13 @@ class PositionSetpointTask(BaseTask):
             el = self.task_config.episode_len_steps
             if el != self._plan_episode_len:
                 self._plan_task.episode_len = self._plan_episode_len = int(el)
+                self._proof_versions = None
+            w = self._proof_watch
+            if w is not None:  # did the host touch what the single-launch proof rests on since the last step?
+                v = (w[0]._version, w[1]._version, w[2]._version, w[3]._version)
+                if v != self._proof_versions or env._calls != self._proof_calls:
+                    self._proof_versions, self._proof_calls = v, env._calls
+                    self._plan.proof_min_tag = (B.step_counter + 1) & 0x7FFFFFFF  # only records of this step on count
             try:
                 rc = self._plan_fn(self._plan_ref, actions.data_ptr(), _lib.current_stream(env.device))
             finally:

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 12
+#define AGX_ABI_VERSION 13
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -219,6 +219,8 @@ const char *agx_build_id(void);
  *   "env_step_quad"  1 (default): the four-lanes-per-env kernels where they apply; 0: one lane per env everywhere
  *   "ray_split"      0 (default): workgroups per (env, sensor) image by the launch policy (csrc/agx_raycast.hip
  *                    ray_split_policy); n > 0: that many (clamped to the image's tiles)
+ *   "single_launch_step"  1 (default): agx_position_task_step issues a step as ONE launch when its record proves the
+ *                    outcome of the batch-wide reset OR; 0: always the two launches
  * agx_set_option returns AGX_E_ARG for an unknown name or a value out of range; agx_get_option reads the current value.  */
 int agx_set_option(const char *name, int value);
 int agx_get_option(const char *name, int *value);
@@ -257,6 +259,13 @@ typedef struct AgxTaskArgs {
   int32_t *counters;          /* [3] */
   float success_radius;
   int32_t reserved;
+  /* Single-launch position steps (AgxPositionStepPlan.proof_*): set by agx_position_task_step on its own copy for the
+   * four-lanes-per-env kernels; every other caller leaves them zero.                                                        */
+  uint32_t *proof_slots;      /* device [2][blocks][AGX_PROOF_SLOT_WORDS]: what each wave saw at the END of its step       */
+  uint32_t *proof_record;     /* mapped host [AGX_PROOF_RECORD_WORDS]: the previous launch's slots, folded (seqlock)         */
+  uint32_t *proof_violation;  /* device [1]: +1 per broken proof (must stay 0)                                                */
+  float proof_dv;             /* bound on the growth of |v| per env step: (M max|thrust| / mass + |g|) dt 1.1               */
+  int32_t proof_mode;         /* AGX_STEP_TWO / AGX_STEP_ANY / AGX_STEP_NONE: what this launch is                           */
 } AgxTaskArgs;
 
 /* agx_env_step = agx_dynamics_substeps + the task's reward / crash / truncation / reset-set
@@ -514,10 +523,47 @@ int agx_nav_robot_side(const AgxRobotParams *params, const AgxEnvBuffers *buf, i
 int agx_post_step_position(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs,
                            const AgxResetArgs *args, const float *target, float *obs, void *stream);
 
-/* One task.step() of the position-setpoint task as a single host call (two launches:
- * agx_env_step with the position epilogue, then agx_post_step_position).  Toggles
- * buf->flag_parity first, exactly like the host does once per env step.  `plan` only bundles
- * arguments the caller would otherwise pass to those two entry points; nothing is retained.   */
+/* One task.step() of the position-setpoint task as a single host call.  Toggles buf->flag_parity first, exactly like the
+ * host does once per env step.
+ *
+ * Two launches in general: agx_env_step with the position epilogue, then agx_post_step_position.  The second exists because
+ * when ANY env resets, the reference refreshes the derived tensors of EVERY env (base_multirotor.py:205): each observation
+ * depends on an OR over the batch.  When that OR is known before the step is issued, the step is ONE launch
+ * (k_position_step_fused):
+ *   AGX_STEP_ANY   some env certainly resets: step, reset of the env's own flagged envs, refresh and observation per env;
+ *   AGX_STEP_NONE  no env can reset: step and the observation from the pre-step derived tensors.
+ * The proof comes from a record the kernels leave in mapped host memory, read without any HIP synchronisation:
+ *   - every wave stores a slot about the END of its step: a horizon mask (bit k: a "witness" env truncates in step t + k,
+ *     1 <= k <= AGX_PROOF_HORIZON, and cannot crash before), max sim_steps, max |target - p|, max |v|, "some env reset";
+ *   - one extra workgroup of the NEXT launch folds those slots into the record (seqlock: [0] end tag, [1] horizon,
+ *     [2] max sim_steps, [3] max dist bits, [4] max speed bits, [5] flags, [7] begin tag; tag = step_counter + 1 of the
+ *     launch that wrote the slots, 31 bits, 0 = none);
+ *   - agx_step_proof_decide turns the record into the mode of step `now_tag`.
+ * The proof is about what the KERNELS did: the caller voids older records (proof_min_tag = this step's tag) whenever it
+ * touched the state, target, sim_steps or motor-thrust tensors, the episode length, or called anything else on the env.
+ * Two launches, always, for: a stream that is capturing (and every later step of a plan that was captured), the strict-RNG
+ * draws (reset->u_state), a bound step exchange (step_rows, step_signal, peer push), anything the four-lanes-per-env kernel
+ * does not cover, agx_set_option("single_launch_step", 0), proof_* NULL.  Bit-identical in every mode.                    */
+#define AGX_PROOF_HORIZON 31
+#define AGX_PROOF_SLOT_WORDS 8
+#define AGX_PROOF_RECORD_WORDS 8
+enum { AGX_STEP_TWO = 0, AGX_STEP_ANY = 1, AGX_STEP_NONE = 2 };
+/* why a step ran as it did (AgxPositionStepPlan.reason_count) */
+enum {
+  AGX_PROOF_PROVED = 0,       /* ANY or NONE */
+  AGX_PROOF_OFF = 1,          /* option single_launch_step = 0, or no proof buffers in the plan */
+  AGX_PROOF_NOT_COVERED = 2,  /* strict RNG, step exchange, kernel choice: the two launches are the only form */
+  AGX_PROOF_CAPTURE = 3,      /* stream capturing now, or a step of this plan was captured before */
+  AGX_PROOF_NO_RECORD = 4,    /* nothing published yet (tag 0) */
+  AGX_PROOF_TORN = 5,         /* the seqlock read saw a write in progress */
+  AGX_PROOF_VOID = 6,         /* the record is older than the caller's last interference */
+  AGX_PROOF_TAG = 7,          /* the record is not from a step before this one, or more than 64 steps old */
+  AGX_PROOF_RESET_NO_WITNESS = 8, /* some env reset in the recorded step (no "none" proof) and no witness covers this step */
+  AGX_PROOF_MAY_TRUNCATE = 9, /* no witness, and an env may truncate by this step */
+  AGX_PROOF_MAY_CRASH = 10,   /* no witness, and an env may crash by this step */
+  AGX_PROOF_LAG = 11,         /* the host ran more than max_lag steps ahead and the record did not catch up within 2 ms */
+  AGX_PROOF_REASONS = 12
+};
 typedef struct AgxPositionStepPlan {
   const AgxRobotParams *params;
   AgxEnvBuffers *buf;
@@ -527,8 +573,45 @@ typedef struct AgxPositionStepPlan {
   float *obs;          /* [N][13] */
   int32_t num_envs;
   int32_t k_substeps;
+  /* single-launch steps (all three buffers non-NULL to enable) */
+  uint32_t *proof_slots;     /* device, 2 * ceil(num_envs / 16) * AGX_PROOF_SLOT_WORDS words, zero-filled */
+  uint32_t *proof_record;    /* agx_host_record_alloc(AGX_PROOF_RECORD_WORDS * 4) */
+  uint32_t *proof_violation; /* device, 1 word, zero-filled */
+  uint32_t proof_min_tag;    /* in: records with an older tag are void */
+  int32_t max_lag;           /* in: the call does not run more than this many steps ahead of the newest record (it spins on
+                                the record, no HIP call, at most 2 ms); 2 .. AGX_PROOF_HORIZON - 1, 0 = 8               */
+  int32_t captured;          /* out: 1 once a step of this plan was issued into a capturing stream */
+  int32_t slot_run;          /* out: consecutive calls whose launches wrote proof slots */
+  int32_t last_mode;         /* out: AGX_STEP_* of the last call */
+  int32_t last_reason;       /* out: AGX_PROOF_* of the last call */
+  uint64_t mode_count[3];    /* out: calls per AGX_STEP_* */
+  uint64_t reason_count[AGX_PROOF_REASONS]; /* out: calls per AGX_PROOF_* */
 } AgxPositionStepPlan;
-int agx_position_task_step(const AgxPositionStepPlan *plan, const float *actions_in, void *stream);
+int agx_position_task_step(AgxPositionStepPlan *plan, const float *actions_in, void *stream);
+
+/* The host decision of agx_position_task_step, a pure function of the record and the step (CPU tests drive it with
+ * synthetic records).  Returns AGX_STEP_*; *reason = AGX_PROOF_*.                                                       */
+typedef struct AgxStepProofQuery {
+  uint32_t now_tag;            /* the tag THIS step's launch writes: (step_counter + 1) mod 2^31 */
+  uint32_t min_tag;            /* records with an older tag are void */
+  int32_t episode_len;
+  int32_t reset_on_collision;
+  float dt, max_linear_velocity, dv; /* dv: agx_step_proof_dv */
+  int32_t reserved;
+} AgxStepProofQuery;
+int agx_step_proof_decide(const uint32_t *record, const AgxStepProofQuery *query, int32_t *reason);
+/* the bound on the growth of |v| per env step: (num_motors max(|max_thrust|, |min_thrust|) / mass + |g|) dt 1.1 */
+float agx_step_proof_dv(const AgxRobotParams *params);
+/* bounds on how far a robot whose speed is `speed` gets in m env steps, margins included (dist + bound < 8 proves "no crash"):
+ * per_env = 1: m dt min(v_max, speed + m dv) (the witnesses' bound); 0: the sum over the steps of min(v_max, speed + i dv) dt
+ * (the "none" proof's, from the batch's largest speed)                                                                    */
+float agx_step_proof_travel(int m, float speed, float dt, float max_linear_velocity, float dv, int per_env);
+/* the slot's horizon bit of one env at the end of step t (1 << k if it is a witness for step t + k, else 0): the device's rule */
+uint32_t agx_step_proof_witness_bit(int episode_len, int reset_on_collision, int sim_steps, float dist, float speed, float dt,
+                                    float max_linear_velocity, float dv);
+/* Mapped, device-visible, coherent host memory for small records that kernels write and the host polls (zero-filled). */
+int agx_host_record_alloc(size_t bytes, void **out);
+int agx_host_record_free(void *record);
 
 /* ---- the same step in the reference-faithful RNG mode (args={"strict_rng": True}) -------------------------------------
  * The reference consumes torch's generator only on steps on which some env resets (`if len(env_ids) > 0` behind a
