@@ -243,6 +243,8 @@ class AgxPositionStepPlan(C.Structure):
         ("last_reason", C.c_int32),
         ("mode_count", C.c_uint64 * 3),
         ("reason_count", C.c_uint64 * 12),
+        ("lag_wait_ns", C.c_uint64),
+        ("lag_waits", C.c_uint64),
     ]
 
 
@@ -276,7 +278,7 @@ class AgxLinkFrames(C.Structure):
     _fields_ = [("num_bodies", C.c_int32), ("reserved", C.c_int32), ("rot", (C.c_float * 9) * MAX_BODIES), ("pos", (C.c_float * 3) * MAX_BODIES)]
 
 
-ABI_VERSION = 13  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 14  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),

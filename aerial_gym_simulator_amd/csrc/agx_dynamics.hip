@@ -1756,41 +1756,68 @@ AGX_DEV void wave_reset_draws(const AgxResetArgs &R, int i, int ep, bool mine, R
   }
 }
 
-// BaseMultirotor.reset_idx / MotorModel.reset_idx / IsaacGymEnv.reset_idx of ONE env from its draws; returns the new state
+// BaseMultirotor.reset_idx / MotorModel.reset_idx / IsaacGymEnv.reset_idx of ONE env from its draws, in two halves: the values
+// (arithmetic only: the helper wave of k_position_step_fused<AGX_STEP_ANY> evaluates them before it may store anything) ...
 template <int M>
-AGX_DEV EnvState reset_env(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, int ep,
-                           const ResetDraws<M> &D) {
+struct ResetValues {
+  float bmin[3], bmax[3], gains[12], mot[M][4];  // mot[j]: tau_inc, tau_dec, thrust, kT
   EnvState s;
+};
+template <int M>
+AGX_DEV ResetValues<M> reset_env_values(const AgxRobotParams &P, const AgxResetArgs &R, const ResetDraws<M> &D) {
+  ResetValues<M> V;
   // IsaacGymEnv.reset_idx: env bounds first, the robot spawn uses them
-  float bmin[3], bmax[3];
-  bounds_from_draws(R, D.ub, bmin, bmax);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    AGX_AT(B.bounds_min, c) = bmin[c];
-    AGX_AT(B.bounds_max, c) = bmax[c];
-  }
+  bounds_from_draws(R, D.ub, V.bmin, V.bmax);
+  const float *bmin = V.bmin, *bmax = V.bmax;
   float r[13];
 #pragma unroll
   for (int c = 0; c < 13; ++c) r[c] = (R.max_state[c] - R.min_state[c]) * D.us[c] + R.min_state[c];
-  s.p = V3{bmin[0] + (bmax[0] - bmin[0]) * r[0], bmin[1] + (bmax[1] - bmin[1]) * r[1], bmin[2] + (bmax[2] - bmin[2]) * r[2]};
-  s.q = quat_from_euler(r[3], r[4], r[5]);
-  s.v = V3{r[7], r[8], r[9]};
-  s.w = V3{r[10], r[11], r[12]};
-  store_state(B.state, n, i, s);
+  V.s.p = V3{bmin[0] + (bmax[0] - bmin[0]) * r[0], bmin[1] + (bmax[1] - bmin[1]) * r[1], bmin[2] + (bmax[2] - bmin[2]) * r[2]};
+  V.s.q = quat_from_euler(r[3], r[4], r[5]);
+  V.s.v = V3{r[7], r[8], r[9]};
+  V.s.w = V3{r[10], r[11], r[12]};
+#pragma unroll
+  for (int c = 0; c < 12; ++c) V.gains[c] = (R.gains_max[c] - R.gains_min[c]) * D.ug[c] + R.gains_min[c];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    V.mot[j][0] = (R.tau_inc_max - R.tau_inc_min) * D.um[j][0] + R.tau_inc_min;
+    V.mot[j][1] = (R.tau_dec_max - R.tau_dec_min) * D.um[j][1] + R.tau_dec_min;
+    V.mot[j][2] = (P.max_thrust - P.min_thrust) * D.um[j][2] + P.min_thrust;
+    V.mot[j][3] = (R.kT_max - R.kT_min) * D.um[j][3] + R.kT_min;
+  }
+  return V;
+}
+// ... and the stores
+template <int M>
+AGX_DEV void reset_env_store(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, int ep,
+                             const ResetValues<M> &V) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    AGX_AT(B.bounds_min, c) = V.bmin[c];
+    AGX_AT(B.bounds_max, c) = V.bmax[c];
+  }
+  store_state(B.state, n, i, V.s);
   if (R.randomize_gains) {
 #pragma unroll
-    for (int c = 0; c < 12; ++c) AGX_AT(B.gains, c) = (R.gains_max[c] - R.gains_min[c]) * D.ug[c] + R.gains_min[c];
+    for (int c = 0; c < 12; ++c) AGX_AT(B.gains, c) = V.gains[c];
   }
 #pragma unroll
   for (int j = 0; j < M; ++j) {
-    if (B.motor_tau_inc) AGX_AT(B.motor_tau_inc, j) = (R.tau_inc_max - R.tau_inc_min) * D.um[j][0] + R.tau_inc_min;
-    if (B.motor_tau_dec) AGX_AT(B.motor_tau_dec, j) = (R.tau_dec_max - R.tau_dec_min) * D.um[j][1] + R.tau_dec_min;
-    AGX_AT(B.motor_thrust, j) = (P.max_thrust - P.min_thrust) * D.um[j][2] + P.min_thrust;
-    if (P.use_rps) AGX_AT(B.motor_kT, j) = (R.kT_max - R.kT_min) * D.um[j][3] + R.kT_min;
+    if (B.motor_tau_inc) AGX_AT(B.motor_tau_inc, j) = V.mot[j][0];
+    if (B.motor_tau_dec) AGX_AT(B.motor_tau_dec, j) = V.mot[j][1];
+    AGX_AT(B.motor_thrust, j) = V.mot[j][2];
+    if (P.use_rps) AGX_AT(B.motor_kT, j) = V.mot[j][3];
   }
   B.sim_steps[i] = 0;
   if (B.episode_count) B.episode_count[i] = ep + 1;
-  return s;
+}
+// returns the new state
+template <int M>
+AGX_DEV EnvState reset_env(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, int ep,
+                           const ResetDraws<M> &D) {
+  const ResetValues<M> V = reset_env_values<M>(P, R, D);
+  reset_env_store<M>(P, B, n, R, i, ep, V);
+  return V.s;
 }
 
 // What follows the reset decision of one env step, for one env: the masked reset (base_multirotor.py:177-205,
@@ -2030,17 +2057,31 @@ __host__ __device__ inline unsigned proof_witness_bit(int episode_len, int reset
   return w ? (1u << k) : 0u;
 }
 
+// OR (MAX = false) or unsigned max over the 64 lanes of a wave, as a wave-uniform value.  All 64 lanes must be active.
+template <bool MAX>
+AGX_DEV unsigned wave_reduce_dpp(unsigned x) {
+#define AGX_RED(ctrl)                                                                        \
+  {                                                                                           \
+    const unsigned y_ = (unsigned)__builtin_amdgcn_mov_dpp((int)x, (ctrl), 0xF, 0xF, true);   \
+    x = MAX ? max(x, y_) : (x | y_);                                                          \
+  }
+  AGX_RED(0xB1)   // quad_perm:[1,0,3,2]
+  AGX_RED(0x4E)   // quad_perm:[2,3,0,1]
+  AGX_RED(0x124)  // row_ror:4
+  AGX_RED(0x128)  // row_ror:8
+#undef AGX_RED
+  const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)x, 0), r1 = (unsigned)__builtin_amdgcn_readlane((int)x, 16);
+  const unsigned r2 = (unsigned)__builtin_amdgcn_readlane((int)x, 32), r3 = (unsigned)__builtin_amdgcn_readlane((int)x, 48);
+  return MAX ? max(max(r0, r1), max(r2, r3)) : ((r0 | r1) | (r2 | r3));
+}
+
 AGX_DEV void proof_store_slot(const AgxTaskArgs &T, const AgxEnvBuffers &B, int wb, int nb, bool reset, unsigned horizon, int steps,
                               float dist, float speed) {
-  unsigned ar = reset ? 1u : 0u, hz = horizon, ms = (unsigned)max(steps, 0), db = proof_key(dist), vb = proof_key(speed);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ar |= (unsigned)__shfl_xor((int)ar, off);
-    hz |= (unsigned)__shfl_xor((int)hz, off);
-    ms = max(ms, (unsigned)__shfl_xor((int)ms, off));
-    db = max(db, (unsigned)__shfl_xor((int)db, off));
-    vb = max(vb, (unsigned)__shfl_xor((int)vb, off));
-  }
+  // only lane 0 stores: OR and max are idempotent, so four DPP stages leave every lane with its row's value and the four rows
+  // meet in scalar registers -- no trip through the LDS crossbar (a __shfl_xor butterfly is six dependent ds_bpermute stages)
+  const unsigned ar = wave_reduce_dpp<false>(reset ? 1u : 0u), hz = wave_reduce_dpp<false>(horizon);
+  const unsigned ms = wave_reduce_dpp<true>((unsigned)max(steps, 0)), db = wave_reduce_dpp<true>(proof_key(dist));
+  const unsigned vb = wave_reduce_dpp<true>(proof_key(speed));
   if ((threadIdx.x & 63u) == 0u) {
     uint4 *slot = reinterpret_cast<uint4 *>(T.proof_slots + ((size_t)(B.step_counter & 1) * nb + wb) * AGX_PROOF_SLOT_WORDS);
     slot[0] = make_uint4(((unsigned)B.step_counter + 1u) & 0x7FFFFFFFu, ar | (T.proof_mode == AGX_STEP_ANY ? 2u : 0u), hz, ms);
@@ -2098,9 +2139,20 @@ AGX_DEV void proof_fold_publish(const AgxTaskArgs &T, const AgxEnvBuffers &B, in
 //                  k_reset_masked_quad_obs reads back with its flag clear)
 // Same IEEE operations in the same order in every mode (bit-identical); the fused modes write no address from two lanes (the
 // sub-step's state, thrust and sim_steps stores are skipped for an env that reset_env rewrites) and carry no step exchange.
+//
+// ANY runs on two waves per workgroup.  A launch lasts as long as its slowest wave, a lone wave per SIMD issues one instruction
+// after the other, and the reset, the refresh and the observation do not depend on most of what the step computes: they are
+// position_step_helper's, on a SIMD of the same CU that would otherwise idle.  The step wave (this function, wave 0) hands the
+// post-step state and the reset bits over through LDS at ONE workgroup barrier that every wave of an env workgroup reaches
+// unconditionally, and goes on with the reward, the proof slot and its own stores.  NONE and TWO have no such tail and stay
+// one-wave workgroups without an LDS segment.
+struct StepHandoff {
+  float p[64], q[64], v[64], w[64];  // per lane of the step wave: its component of the post-step state
+  int reset[64];                     // the env resets (truncation or crash)
+};
 template <int MODE>
 AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const float *__restrict__ actions_in,
-                                const AgxTaskArgs &T, const AgxResetArgs &R, float *__restrict__ obs) {
+                                const AgxTaskArgs &T, float *__restrict__ obs, StepHandoff *H) {
   constexpr bool FUSED = MODE != AGX_STEP_TWO;
   const int tid = threadIdx.x;
   const bool proof = T.proof_slots != nullptr;
@@ -2118,18 +2170,22 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
   if (!FUSED && wb == 0) push_publish_previous(B);  // peer push: the previous step's rows have landed everywhere
   const uint32_t push_peek = (!FUSED && wb == 0) ? push_wait_peek(B) : 0u;  // ... and this step's slot: looked at when the kernel is done
   float p = 0.0f, q = 0.0f, v = 0.0f, w = 0.0f, tgt = 0.0f, vbody = 0.0f, wbody = 0.0f;
-  int steps = 0, ep = 0;
+  int steps = 0;
   float proof_dist = 0.0f, proof_speed = 0.0f;
   unsigned horizon = 0u;
+  // what the second half of the step (behind ANY's hand-off) takes over from the first
+  float u[1] = {0.0f}, a_in = 0.0f, a_old = 0.0f, fz = 0.0f, torque = 0.0f, dist = 0.0f;
+  QuadDerived d{};
+  bool crashed = false, trunc = false;
   if (valid) {
     // ---- loads: one instruction per vector
     p = AGX_QAT(B.state, 0, ol3); q = AGX_QAT(B.state, 3, ol); v = AGX_QAT(B.state, 7, ol3); w = AGX_QAT(B.state, 10, ol3);
-    float u[1] = {AGX_QAT(B.motor_thrust, 0, ol)};  // motor l
+    u[0] = AGX_QAT(B.motor_thrust, 0, ol);  // motor l
     const float kT[1] = {P.use_rps ? AGX_QAT(B.motor_kT, 0, ol) : 1.0f};
     const float tinc[1] = {B.motor_tau_inc ? AGX_QAT(B.motor_tau_inc, 0, ol) : P.tau_inc_uniform};
     const float tdec[1] = {B.motor_tau_dec ? AGX_QAT(B.motor_tau_dec, 0, ol) : P.tau_dec_uniform};
-    const float a_in = actions_in[(size_t)i * 4 + l];
-    const float a_old = AGX_QAT(B.actions, 0, ol);
+    a_in = actions_in[(size_t)i * 4 + l];
+    a_old = AGX_QAT(B.actions, 0, ol);
     const float kp = B.gains ? AGX_QAT(B.gains, 0, ol3) : P.gains_uniform[0 + l3];
     const float kv = B.gains ? AGX_QAT(B.gains, 3, ol3) : P.gains_uniform[3 + l3];
     const float kr = B.gains ? AGX_QAT(B.gains, 6, ol3) : P.gains_uniform[6 + l3];
@@ -2139,21 +2195,20 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
     // path -- one that also waits for every store in front of it (gfx9 counts loads and stores in the same vmcnt)
     const int steps_in = B.sim_steps[i];
     tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
-    if (MODE == AGX_STEP_ANY && B.episode_count) ep = B.episode_count[i];  // (the reset's draws are keyed by it)
     const QuadConsts<4> C = load_quad_consts<4>(P, l, l3);
 
     // ---- update_states + controller (position_control.py:20-51)
     const float a = clamp_minmax(a_in, -10.0f, 10.0f);  // clip_actions
     float sy_sp, cy_sp;  // of the yaw set-point (lanes 0, 1), out of the evaluation that serves the vehicle-frame quaternion
-    const QuadDerived d = update_states_quad(q, v, w, q4::bc<3>(a), sy_sp, cy_sp);
+    d = update_states_quad(q, v, w, q4::bc<3>(a), sy_sp, cy_sp);
     // compute_acceleration (velocity set-point 0): kp (sp - p) + kv (0 - v)
     const float pe = a - p;
     const float ve = 0.0f - v;
     const float acc = kp * pe + kv * ve;
     const float f = (acc - C.grav) * C.mass;
-    const float fz = quad_thrust_along_body_z(q, f, l);
+    fz = quad_thrust_along_body_z(q, f, l);
     const float qd = quad_desired_orientation_pos_vel_sc(f, sy_sp, cy_sp, l);
-    const float torque = quad_body_torque<true>(C, q, qd, d.wbody, 0.0f, kr, kw, l);
+    torque = quad_body_torque<true>(C, q, qd, d.wbody, 0.0f, kr, kw, l);
 
     // ---- allocation + motor model + body wrench, rigid-body update
     float fb, tb;
@@ -2161,13 +2216,25 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
     if (B.body_force && l < 3) AGX_QAT(B.body_force, 0, ol) = fb;
     quad_integrate(P, C, p, q, v, w, fb, tb, l);
 
-    // ---- EnvManager bookkeeping + the position task's reward / truncation / reset set (position_setpoint_task.py:245-282)
+    // ---- EnvManager bookkeeping + the reset set of the position task (position_setpoint_task.py:245-282)
     steps = steps_in + 1;
-    bool crashed = false, trunc = false;
-    float rew = 0.0f;
     if (T.kind == AGX_TASK_POSITION) {
       const float pe_t = q4::quat_apply(q4::conj(d.qveh), tgt - p);  // quat_apply_inverse
-      const float dist = q4::norm3(pe_t);
+      dist = q4::norm3(pe_t);
+      if (dist > 8.0f) crashed = true;
+      trunc = steps > T.episode_len;
+      reset = (crashed && T.reset_on_collision) || trunc;
+    }
+  }
+  if (MODE == AGX_STEP_ANY) {  // the hand-off to the helper wave: every lane of every env workgroup, whatever `valid` says
+    H->p[tid] = p; H->q[tid] = q; H->v[tid] = v; H->w[tid] = w;
+    H->reset[tid] = reset ? 1 : 0;
+    __syncthreads();
+  }
+  if (valid) {
+    // ---- the position task's reward
+    float rew = 0.0f;
+    if (T.kind == AGX_TASK_POSITION) {
       // 3 exp(-8 d^2) + 2 exp(-4 d^2): both exponentials in one evaluation (lanes 0 / 1)
       const float ex = exp_cw((l == 0 ? -8.0f : -4.0f) * dist * dist);
       const float pos_reward = 3.0f * q4::bc<0>(ex) + 2.0f * q4::bc<1>(ex);
@@ -2182,11 +2249,8 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
       const float ang_reward = q4::bc<1>(quo);
       float total = pos_reward + dist_reward + pos_reward * (up_reward + ang_reward);
       total = 1.0f * total;
-      if (dist > 8.0f) crashed = true;
       if (crashed) total = -20.0f;
       rew = total;
-      trunc = steps > T.episode_len;
-      reset = (crashed && T.reset_on_collision) || trunc;
       proof_dist = dist;
     }
     if (proof) {
@@ -2246,36 +2310,7 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
     if (wb == 0) push_wait_finish(B, push_peek);
     return;
   }
-  if (MODE == AGX_STEP_ANY) {
-    // k_reset_masked_quad_obs with its flag set (reset_masked_quad_obs_body<false>): the env's own reset ...
-    const bool mine = reset;
-    const bool lead = mine && l == 0;
-    ResetDraws<4> D{};
-    wave_reset_draws<4>(R, B.env_index_base + i, ep, lead, D);  // draws are keyed by the GLOBAL env index
-    if (some) {
-      EnvState s{};
-      if (lead) s = reset_env<4>(P, B, n, R, i, ep, D);
-      // the quad takes the new state over from its first lane
-      const float npv = q4::by_lane(l3, q4::bc<0>(s.p.x), q4::bc<0>(s.p.y), q4::bc<0>(s.p.z));
-      const float nq = q4::by_lane(l, q4::bc<0>(s.q.x), q4::bc<0>(s.q.y), q4::bc<0>(s.q.z), q4::bc<0>(s.q.w));
-      const float nv = q4::by_lane(l3, q4::bc<0>(s.v.x), q4::bc<0>(s.v.y), q4::bc<0>(s.v.z));
-      const float nw = q4::by_lane(l3, q4::bc<0>(s.w.x), q4::bc<0>(s.w.y), q4::bc<0>(s.w.z));
-      p = mine ? npv : p; q = mine ? nq : q; v = mine ? nv : v; w = mine ? nw : w;
-    }
-    // ... and BaseMultirotor.reset_idx's un-indexed update_states(): every env is refreshed
-    const QuadDerived d2 = update_states_quad(q, v, w);
-    if (valid) {
-      if (l < 3) {
-        AGX_QAT(B.derived, 0, ol) = d2.euler;
-        AGX_QAT(B.derived, 7, ol) = d2.vveh;
-        AGX_QAT(B.derived, 10, ol) = d2.vbody;
-        AGX_QAT(B.derived, 13, ol) = d2.wbody;
-      }
-      AGX_QAT(B.derived, 3, ol) = d2.qveh;
-    }
-    vbody = d2.vbody;
-    wbody = d2.wbody;
-  }
+  if (MODE == AGX_STEP_ANY) return;  // the reset, the refresh and the observation are the helper wave's
   if (valid) {  // position_setpoint_task.py:194-203: target - p | q | v_body | w_body
     float *o = obs + (size_t)i * 13;
     const float e = tgt - p;
@@ -2284,17 +2319,100 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
   }
 }
 
+// The helper wave (wave 1) of an env workgroup of k_position_step_fused<AGX_STEP_ANY>: what k_reset_masked_quad_obs does with
+// its flag set (reset_masked_quad_obs_body<false>), same lane layout as the step wave, in two phases around the one barrier:
+//   1  while the step wave computes: truncation is `sim_steps + 1 > episode_len`, known from a load, so the draws and the new
+//      state of a truncating env are evaluated here -- into registers: reset_env's stores hit addresses the step wave loads at
+//      its top, and nothing orders the two waves before the barrier;
+//   2  behind the barrier: the envs that crashed (known only after the step) get their draws and values now, reset_env's
+//      stores go out, then BaseMultirotor.reset_idx's un-indexed update_states() of every env and the observation.
+// Every address stored here belongs to a resetting env (the step wave skips those: `own`) or is a derived tensor / the
+// observation (the step wave writes neither in ANY).  Draws are keyed by (seed, global env, episode, stream, block): evaluating
+// them for the truncating and the crashing envs in two calls gives the same values as one call for both.
+AGX_DEV void position_step_helper(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxTaskArgs &T, const AgxResetArgs &R,
+                                  float *__restrict__ obs, const StepHandoff *H) {
+  const bool proof = T.proof_slots != nullptr;
+  if (proof && blockIdx.x == 0) return;  // the folding workgroup: wave 0's, and no barrier in it
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wb = (int)blockIdx.x - (proof ? 1 : 0);  // env block
+  const int l = lane & 3, l3 = l < 3 ? l : 2;
+  const int i = wb * 16 + (lane >> 2);  // env
+  const unsigned ol = ((unsigned)l * (unsigned)n + (unsigned)i) * 4u, ol3 = ((unsigned)l3 * (unsigned)n + (unsigned)i) * 4u;  // AGX_QAT
+  const bool valid = i < n;
+  int steps_in = 0, ep = 0;
+  float tgt = 0.0f;
+  if (valid) {
+    steps_in = B.sim_steps[i];
+    if (B.episode_count) ep = B.episode_count[i];  // (the reset's draws are keyed by it)
+    tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
+  }
+  // ---- phase 1: the step wave's own truncation predicate
+  const bool early = valid && T.kind == AGX_TASK_POSITION && steps_in + 1 > T.episode_len;
+  ResetValues<4> V{};
+  if (vote(early) != 0ull) {
+    ResetDraws<4> D{};
+    wave_reset_draws<4>(R, B.env_index_base + i, ep, early && l == 0, D);  // draws are keyed by the GLOBAL env index
+    V = reset_env_values<4>(P, R, D);
+  }
+  __syncthreads();
+  // ---- phase 2
+  float p = H->p[lane], q = H->q[lane], v = H->v[lane], w = H->w[lane];
+  const bool mine = H->reset[lane] != 0;
+  const bool late = mine && !early;  // a crash
+  if (vote(late) != 0ull) {
+    ResetDraws<4> D{};
+    wave_reset_draws<4>(R, B.env_index_base + i, ep, late && l == 0, D);
+    const ResetValues<4> V2 = reset_env_values<4>(P, R, D);
+    if (late) V = V2;
+  }
+  if (vote(mine) != 0ull) {  // some env of this wave resets
+    if (mine && l == 0) reset_env_store<4>(P, B, n, R, i, ep, V);
+    // the quad takes the new state over from its first lane
+    const EnvState &s = V.s;
+    const float npv = q4::by_lane(l3, q4::bc<0>(s.p.x), q4::bc<0>(s.p.y), q4::bc<0>(s.p.z));
+    const float nq = q4::by_lane(l, q4::bc<0>(s.q.x), q4::bc<0>(s.q.y), q4::bc<0>(s.q.z), q4::bc<0>(s.q.w));
+    const float nv = q4::by_lane(l3, q4::bc<0>(s.v.x), q4::bc<0>(s.v.y), q4::bc<0>(s.v.z));
+    const float nw = q4::by_lane(l3, q4::bc<0>(s.w.x), q4::bc<0>(s.w.y), q4::bc<0>(s.w.z));
+    p = mine ? npv : p; q = mine ? nq : q; v = mine ? nv : v; w = mine ? nw : w;
+  }
+  // BaseMultirotor.reset_idx ends with an un-indexed update_states(): every env is refreshed
+  const QuadDerived d2 = update_states_quad(q, v, w);
+  if (valid) {
+    if (l < 3) {
+      AGX_QAT(B.derived, 0, ol) = d2.euler;
+      AGX_QAT(B.derived, 7, ol) = d2.vveh;
+      AGX_QAT(B.derived, 10, ol) = d2.vbody;
+      AGX_QAT(B.derived, 13, ol) = d2.wbody;
+    }
+    AGX_QAT(B.derived, 3, ol) = d2.qveh;
+    // position_setpoint_task.py:194-203: target - p | q | v_body | w_body
+    float *o = obs + (size_t)i * 13;
+    const float e = tgt - p;
+    if (l < 3) { o[l] = e; o[7 + l] = d2.vbody; o[10 + l] = d2.wbody; }
+    o[3 + l] = q;
+  }
+}
+
 __global__ void __launch_bounds__(64, 1)
     k_env_step_quad_position(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, AgxTaskArgs T) {
-  position_step_quad<AGX_STEP_TWO>(P, B, n, actions_in, T, AgxResetArgs{}, nullptr);
+  position_step_quad<AGX_STEP_TWO>(P, B, n, actions_in, T, nullptr, nullptr);
 }
 
 // The whole position step as ONE launch (agx_position_task_step, when the host record proves the outcome of the batch-wide reset
-// OR): AGX_STEP_ANY or AGX_STEP_NONE, always with the proof slots and the folding workgroup 0.
+// OR): AGX_STEP_ANY or AGX_STEP_NONE, always with the proof slots and the folding workgroup 0.  ANY: 128 threads, the step wave
+// and its helper wave (position_step_quad); both waves of the folding workgroup return before any barrier.
 template <int MODE>
-__global__ void __launch_bounds__(64, 1) k_position_step_fused(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in,
-                                                               AgxTaskArgs T, AgxResetArgs R, float *__restrict__ obs) {
-  position_step_quad<MODE>(P, B, n, actions_in, T, R, obs);
+__global__ void __launch_bounds__(MODE == AGX_STEP_ANY ? 128 : 64, 1)
+    k_position_step_fused(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, AgxTaskArgs T, AgxResetArgs R,
+                          float *__restrict__ obs) {
+  if constexpr (MODE == AGX_STEP_ANY) {
+    __shared__ StepHandoff H;
+    // (readfirstlane: a scalar branch -- each wave runs one side only and meets exactly one s_barrier)
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) position_step_quad<MODE>(P, B, n, actions_in, T, obs, &H);
+    else position_step_helper(P, B, n, T, R, obs, &H);
+  } else {
+    position_step_quad<MODE>(P, B, n, actions_in, T, obs, nullptr);
+  }
 }
 
 // AssetManager.reset_idx (asset_manager.py:51-71) + the half-obstacle resample (env_manager.py:283-295)
@@ -2797,15 +2915,22 @@ static int position_step_mode(AgxPositionStepPlan *plan, const AgxTaskArgs &T, h
     uint32_t k = (Q.now_tag - h[0]) & 0x7FFFFFFFu;
     if (h[0] != 0u && k > (uint32_t)max_lag && k <= 64u) {
       const auto t0 = std::chrono::steady_clock::now();
+      // (lag_wait_ns / lag_waits: how much of the host's step time is this wait -- what is left is the host's own floor)
+      const auto waited = [&] {
+        plan->lag_waits += 1;
+        plan->lag_wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+      };
       for (unsigned spin = 1;; ++spin) {
         k = (Q.now_tag - h[0]) & 0x7FFFFFFFu;
         if (k <= (uint32_t)max_lag || k > 64u) break;
         __builtin_ia32_pause();
         if ((spin & 255u) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) {
+          waited();
           *reason = AGX_PROOF_LAG;
           return AGX_STEP_TWO;
         }
       }
+      waited();
     }
   }
   return agx_step_proof_decide(plan->proof_record, &Q, reason);
@@ -2847,8 +2972,8 @@ extern "C" int agx_position_task_step(AgxPositionStepPlan *plan, const float *ac
                 "null buffer");
     const dim3 grid(blocks_for(n, 16) + 1);
     if (mode == AGX_STEP_ANY)
-      hipLaunchKernelGGL(k_position_step_fused<AGX_STEP_ANY>, grid, dim3(64), 0, (hipStream_t)stream, *plan->params, *B, n, actions_in, T,
-                         *plan->reset, plan->obs);
+      hipLaunchKernelGGL(k_position_step_fused<AGX_STEP_ANY>, grid, dim3(128), 0, (hipStream_t)stream, *plan->params, *B, n, actions_in, T,
+                         *plan->reset, plan->obs);  // (the step wave and its helper wave)
     else
       hipLaunchKernelGGL(k_position_step_fused<AGX_STEP_NONE>, grid, dim3(64), 0, (hipStream_t)stream, *plan->params, *B, n, actions_in, T,
                          *plan->reset, plan->obs);

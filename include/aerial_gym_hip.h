@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 13
+#define AGX_ABI_VERSION 14
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -586,6 +586,8 @@ typedef struct AgxPositionStepPlan {
   int32_t last_reason;       /* out: AGX_PROOF_* of the last call */
   uint64_t mode_count[3];    /* out: calls per AGX_STEP_* */
   uint64_t reason_count[AGX_PROOF_REASONS]; /* out: calls per AGX_PROOF_* */
+  uint64_t lag_wait_ns;      /* out: time spent spinning on the record because the call was max_lag steps ahead of it */
+  uint64_t lag_waits;        /* out: entries into that spin loop */
 } AgxPositionStepPlan;
 int agx_position_task_step(AgxPositionStepPlan *plan, const float *actions_in, void *stream);
 
