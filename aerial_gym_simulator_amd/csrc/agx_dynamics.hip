@@ -139,6 +139,46 @@ AGX_DEV T &soa_at_off(T *base, int c, int n, unsigned off_bytes) {
 //  the `pointer ? load : uniform` arms add; the one-lane kernels are bound by throughput and registers, where they pay.)
 #define AGX_QAT(p, c, off) agx::soa_at_off((p), (c), n, (off))
 
+// Kernel arguments of the position-step kernels, fetched as ONE batch per wave.  A kernel-argument field is a load from constant
+// memory that the compiler emits where the field is used: in a kernel of many basic blocks that is one s_load and one
+// `s_waitcnt lgkmcnt(0)` -- a full scalar-memory round trip that a lone wave per SIMD sits out -- in nearly every block, one in
+// front of nearly every group of stores.  arg_pin() reads the field HERE and passes it through an empty volatile asm that takes
+// and returns it in scalar registers: the compiler cannot re-load it later (it no longer knows where the value came from) and
+// cannot sink the asm, so the fields pinned back to back at the top of a wave are fetched by a few wide s_loads under one wait
+// and live in SGPRs from there.  A pointer is pinned as a GLOBAL-address-space pointer: what the compiler knows about a pointer
+// kernel argument and would not know about an opaque 64-bit value (a generic pointer: flat_load / flat_store).
+// The fetch is written in two passes over one list of fields -- every field read into a local, then every local pinned -- because
+// the pins keep their order and a read placed between two pins is issued behind the wait of the first: a second round trip.
+// 
+#define AGX_ARG_READ(S, f) auto S##_##f = S##0 .f;
+#define AGX_ARG_READ_N(S, f, N) \
+  float S##_##f[N];             \
+  _Pragma("unroll") for (int k_ = 0; k_ < N; ++k_) S##_##f[k_] = S##0 .f[k_];
+#define AGX_ARG_PIN(S, f) \
+  arg_pin(S##_##f);       \
+  S.f = S##_##f;
+#define AGX_ARG_PIN_N(S, f, N) \
+  _Pragma("unroll") for (int k_ = 0; k_ < N; ++k_) { arg_pin(S##_##f[k_]); S.f[k_] = S##_##f[k_]; }
+template <class T>
+AGX_DEV void arg_pin(T &x) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
+  asm volatile("" : "+s"(x));
+}
+template <class T>
+AGX_DEV void arg_pin(T *&p) {
+  typedef T __attribute__((address_space(1))) *global_ptr;
+  global_ptr g = (global_ptr)p;
+  asm volatile("" : "+s"(g));
+  p = (T *)g;
+}
+// a relaxed atomic load of the narrowest scope: an ordinary global_load that stays one (never merged with another load)
+AGX_DEV float gain_load(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+template <class T, int N>
+AGX_DEV void arg_pin(T (&a)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) arg_pin(a[k]);
+}
+
 AGX_DEV EnvState load_state(const float *__restrict__ s, int n, int i) {
   EnvState e;
   e.p = V3{AGX_AT(s, 0), AGX_AT(s, 1), AGX_AT(s, 2)};
@@ -809,8 +849,10 @@ template <int M>
 struct QuadConsts {
   float grav, in0, in1, in2, ii0, ii1, ii2, pinv[M / 4][6], mapf[M], mapt[M], mass, dt;
 };
+// (S: where the scalar fields come from -- the position-step kernels hand in their pinned copy, see arg_pin; the indexed
+// loads must stay on the kernel argument itself)
 template <int M>
-AGX_DEV QuadConsts<M> load_quad_consts(const AgxRobotParams &P, int l, int l3) {
+AGX_DEV QuadConsts<M> load_quad_consts(const AgxRobotParams &P, const AgxRobotParams &S, int l, int l3) {
   QuadConsts<M> C;
   C.grav = P.gravity[l3];
   C.in0 = P.inertia[3 * l3 + 0]; C.in1 = P.inertia[3 * l3 + 1]; C.in2 = P.inertia[3 * l3 + 2];
@@ -819,15 +861,19 @@ AGX_DEV QuadConsts<M> load_quad_consts(const AgxRobotParams &P, int l, int l3) {
   for (int h = 0; h < M / 4; ++h)
 #pragma unroll
     for (int c = 0; c < 6; ++c) C.pinv[h][c] = P.alloc_pinv[6 * (l + 4 * h) + c];  // motor l + 4 h
-  const float *wmap = P.root_link_mode != 0 ? P.alloc : P.wrench_map;
+  const float *wmap = S.root_link_mode != 0 ? P.alloc : P.wrench_map;
 #pragma unroll
   for (int j = 0; j < M; ++j) {
     C.mapf[j] = wmap[M * l3 + j];        // force row l
     C.mapt[j] = wmap[M * (3 + l3) + j];  // torque row l
   }
-  C.mass = P.mass;
-  C.dt = P.dt;
+  C.mass = S.mass;
+  C.dt = S.dt;
   return C;
+}
+template <int M>
+AGX_DEV QuadConsts<M> load_quad_consts(const AgxRobotParams &P, int l, int l3) {
+  return load_quad_consts<M>(P, P, l, l3);
 }
 // f . third column of quat_to_rotmat(q) = (2 (xz + yw), 2 (yz - xw), 1 - 2 (xx + yy)): the thrust command of the Lee laws
 AGX_DEV float quad_thrust_along_body_z(float q, float f, int l) {
@@ -2032,6 +2078,25 @@ __global__ void __launch_bounds__(64, 1) k_reset_masked_quad_obs_host_draws(AgxR
   reset_masked_quad_obs_body<true>(P, B, n, R, target, obs);
 }
 
+// -DAGX_STEP_STAMPS (profiles/step_phase_probe.py; never in the product build): lane 0 of every wave of a position-step launch
+// stamps the shader clock at six points -- 0 wave start, 1 arguments there / first input load issued, 2 inputs arrived (the
+// stamped build waits for them there), 3 barrier reached (NONE / TWO: the step is computed), 4 barrier passed, 5 last store
+// issued -- and the 100 MHz wall clock at start and end ([6], [7]: cycles -> ns, and who finishes last), with plain vector stores.
+#ifdef AGX_STEP_STAMPS
+constexpr int kStampBlocks = 1024, kStampWords = 8;
+__device__ unsigned long long g_step_stamps[kStampBlocks * 2 * kStampWords];
+AGX_DEV void step_stamp(int k) {
+  const unsigned long long t = k < 6 ? (unsigned long long)clock64() : (unsigned long long)wall_clock64();
+  if ((threadIdx.x & 63u) == 0u && blockIdx.x < (unsigned)kStampBlocks)
+    g_step_stamps[((size_t)blockIdx.x * 2 + (threadIdx.x >> 6)) * kStampWords + k] = t;
+}
+#define AGX_STAMP(k) step_stamp(k)
+#define AGX_STAMP_ARRIVED(k) do { __builtin_amdgcn_s_waitcnt(0); step_stamp(k); } while (0)
+#else
+#define AGX_STAMP(k) do { } while (0)
+#define AGX_STAMP_ARRIVED(k) do { } while (0)
+#endif
+
 // ---- single-launch position steps: the proof record (include/aerial_gym_hip.h, AgxPositionStepPlan) ---------------------------
 // Every wave of a position-step launch of a plan leaves a slot about the END of its step, double-buffered by the step's parity
 // (the folding workgroup of launch u reads bank (u - 1) & 1 while the waves of launch u write bank u & 1):
@@ -2151,13 +2216,50 @@ struct StepHandoff {
   int reset[64];                     // the env resets (truncation or crash)
 };
 template <int MODE>
-AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const float *__restrict__ actions_in,
-                                const AgxTaskArgs &T, float *__restrict__ obs, StepHandoff *H) {
+AGX_DEV void position_step_quad(const AgxRobotParams &P0, const AgxEnvBuffers &B0, int n, const float *actions_in,
+                                const AgxTaskArgs &T0, float *obs, StepHandoff *H) {
   constexpr bool FUSED = MODE != AGX_STEP_TWO;
   const int tid = threadIdx.x;
+  AGX_STAMP(0); AGX_STAMP(6);
+  // ---- kernel arguments: every field this wave uses, one batch (arg_pin).  P / B / T are the pinned copies; P0 / B0 / T0 serve
+  // only what indexes an argument array by lane (vector loads: load_quad_consts, the peer-push flag pointers) and the folding
+  // workgroup
+  AgxRobotParams P = P0;
+  AgxEnvBuffers B = B0;
+  AgxTaskArgs T = T0;
+#define AGX_STEP_WAVE_ARGS(X)                                                                                                        \
+  X(B, state) X(B, actions) X(B, prev_actions) X(B, motor_thrust) X(B, motor_kT) X(B, motor_tau_inc) X(B, motor_tau_dec)  \
+  X(B, gains) X(B, wrench_cmd) X(B, crashes) X(B, truncations) X(B, sim_steps) X(B, reset_mask) X(B, reset_flag) X(B, flag_parity)    \
+  X(B, step_counter) X(B, body_force)                                                                                                  \
+  X(P, dt) X(P, dt_over_6) X(P, mass) X(P, min_thrust) X(P, max_thrust) X(P, max_rate) X(P, linear_damping) X(P, angular_damping)     \
+  X(P, max_linear_velocity) X(P, max_angular_velocity) X(P, tau_inc_uniform) X(P, tau_dec_uniform)                                    \
+  X(T, episode_len) X(T, target) X(T, reward) X(T, proof_slots) X(T, proof_violation) X(T, proof_dv)
+  AGX_STEP_WAVE_ARGS(AGX_ARG_READ)
+  AGX_ARG_READ(B, derived) AGX_ARG_READ(B, push_world)
+  AGX_ARG_READ(P, root_link_mode) AGX_ARG_READ(P, use_rps) AGX_ARG_READ(P, use_discrete_approximation) AGX_ARG_READ(P, integration_rk4)
+  AGX_ARG_READ(T, reset_on_collision) AGX_ARG_READ(T, kind) AGX_ARG_READ(T, proof_mode)
+  const int grid_blocks = (int)gridDim.x;  // (an implicit argument: fetched with the rest, not in front of the proof slot's stores)
+  // nothing crosses this line when the instructions are scheduled: every read above is issued before the first value is looked
+  // at below (otherwise the scheduler defers some of the reads behind the first pin's wait: a second and a third round trip)
+  __builtin_amdgcn_sched_barrier(0);
+  int env_blocks = grid_blocks - 1;
+  // the switches and the small enumerations share ONE register (the one-wave kernels have none to spare: 102, no spills)
+  int sw = (P_root_link_mode != 0 ? 1 : 0) | (P_use_rps != 0 ? 2 : 0) | (P_use_discrete_approximation != 0 ? 4 : 0) |
+           (P_integration_rk4 != 0 ? 8 : 0) | (T_reset_on_collision != 0 ? 16 : 0) | ((T_kind & 0xFF) << 8) | ((T_proof_mode & 0xFF) << 16);
+  arg_pin(n); arg_pin(actions_in);
+  if (MODE == AGX_STEP_NONE) arg_pin(obs);
+  AGX_STEP_WAVE_ARGS(AGX_ARG_PIN)
+  if (MODE != AGX_STEP_ANY) { AGX_ARG_PIN(B, derived) }
+  if (!FUSED) { AGX_ARG_PIN(B, push_world) }
+  arg_pin(env_blocks);
+#undef AGX_STEP_WAVE_ARGS
+  arg_pin(sw);
+  P.root_link_mode = sw & 1; P.use_rps = sw & 2; P.use_discrete_approximation = sw & 4; P.integration_rk4 = sw & 8;
+  T.reset_on_collision = sw & 16; T.kind = (sw >> 8) & 0xFF; T.proof_mode = (sw >> 16) & 0xFF;
   const bool proof = T.proof_slots != nullptr;
   if (proof && blockIdx.x == 0) {  // the extra workgroup of a launch with slots: no envs, only the host record
-    proof_fold_publish(T, B, (int)gridDim.x - 1);
+    proof_fold_publish(T0, B0, (int)gridDim.x - 1);
+    AGX_STAMP(5); AGX_STAMP(7);
     return;
   }
   const int wb = (int)blockIdx.x - (proof ? 1 : 0);  // env block
@@ -2167,8 +2269,14 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
   const bool valid = i < n;
   bool reset = false;
   if (FUSED && wb == 0 && tid == 0) B.reset_flag[B.flag_parity ^ 1] = 0;  // (what the second launch does first)
-  if (!FUSED && wb == 0) push_publish_previous(B);  // peer push: the previous step's rows have landed everywhere
-  const uint32_t push_peek = (!FUSED && wb == 0) ? push_wait_peek(B) : 0u;  // ... and this step's slot: looked at when the kernel is done
+  // peer push (one wave of the launch, sharded runs only: the unlikely side, laid out behind the kernel's own path), decided on
+  // the pinned word: no argument fetch here without it
+  const bool push = !FUSED && wb == 0 && B.push_world > 0;
+  uint32_t push_peek = 0u;
+  if (__builtin_expect(push, false)) {
+    push_publish_previous(B0);        // the previous step's rows have landed everywhere
+    push_peek = push_wait_peek(B0);  // ... and this step's slot: looked at when the kernel is done
+  }
   float p = 0.0f, q = 0.0f, v = 0.0f, w = 0.0f, tgt = 0.0f, vbody = 0.0f, wbody = 0.0f;
   int steps = 0;
   float proof_dist = 0.0f, proof_speed = 0.0f;
@@ -2177,25 +2285,33 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
   float u[1] = {0.0f}, a_in = 0.0f, a_old = 0.0f, fz = 0.0f, torque = 0.0f, dist = 0.0f;
   QuadDerived d{};
   bool crashed = false, trunc = false;
+  AGX_STAMP(1);
   if (valid) {
-    // ---- loads: one instruction per vector
+    // ---- loads: one instruction per vector, all of them issued before any is looked at (one memory round trip).  A buffer
+    // that may be absent is a branch on its wave-uniform pointer around a load that replaces the uniform value (the gains: the
+    // lane's component, an indexed kernel-argument load issued in any case -- twelve scalar registers would not fit): a
+    // `pointer ? global[...] : P.uniform[...]` select compiled to a FLAT load through a selected address, and flat loads count
+    // on lgkmcnt too -- every later wait for a scalar load also sat out those vector loads' trip to memory
     p = AGX_QAT(B.state, 0, ol3); q = AGX_QAT(B.state, 3, ol); v = AGX_QAT(B.state, 7, ol3); w = AGX_QAT(B.state, 10, ol3);
     u[0] = AGX_QAT(B.motor_thrust, 0, ol);  // motor l
-    const float kT[1] = {P.use_rps ? AGX_QAT(B.motor_kT, 0, ol) : 1.0f};
-    const float tinc[1] = {B.motor_tau_inc ? AGX_QAT(B.motor_tau_inc, 0, ol) : P.tau_inc_uniform};
-    const float tdec[1] = {B.motor_tau_dec ? AGX_QAT(B.motor_tau_dec, 0, ol) : P.tau_dec_uniform};
+    float kT[1] = {1.0f}, tinc[1] = {P.tau_inc_uniform}, tdec[1] = {P.tau_dec_uniform};
+    if (P.use_rps) kT[0] = AGX_QAT(B.motor_kT, 0, ol);
+    if (B.motor_tau_inc) tinc[0] = AGX_QAT(B.motor_tau_inc, 0, ol);
+    if (B.motor_tau_dec) tdec[0] = AGX_QAT(B.motor_tau_dec, 0, ol);
     a_in = actions_in[(size_t)i * 4 + l];
     a_old = AGX_QAT(B.actions, 0, ol);
-    const float kp = B.gains ? AGX_QAT(B.gains, 0, ol3) : P.gains_uniform[0 + l3];
-    const float kv = B.gains ? AGX_QAT(B.gains, 3, ol3) : P.gains_uniform[3 + l3];
-    const float kr = B.gains ? AGX_QAT(B.gains, 6, ol3) : P.gains_uniform[6 + l3];
-    const float kw = B.gains ? AGX_QAT(B.gains, 9, ol3) : P.gains_uniform[9 + l3];
+    float kp = P0.gains_uniform[0 + l3], kv = P0.gains_uniform[3 + l3], kr = P0.gains_uniform[6 + l3], kw = P0.gains_uniform[9 + l3];
+    if (B.gains) {  // (gain_load: not a load the compiler may fold with the one above into a flat load of a selected address)
+      kp = gain_load(&AGX_QAT(B.gains, 0, ol3)); kv = gain_load(&AGX_QAT(B.gains, 3, ol3));
+      kr = gain_load(&AGX_QAT(B.gains, 6, ol3)); kw = gain_load(&AGX_QAT(B.gains, 9, ol3));
+    }
     // what the task epilogue reads is requested HERE, with the state: behind the stores below the compiler cannot move a load up
     // (the buffers may alias for all it knows), and a load issued there is a second memory round trip on the kernel's critical
     // path -- one that also waits for every store in front of it (gfx9 counts loads and stores in the same vmcnt)
     const int steps_in = B.sim_steps[i];
     tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
-    const QuadConsts<4> C = load_quad_consts<4>(P, l, l3);
+    const QuadConsts<4> C = load_quad_consts<4>(P0, P, l, l3);
+    AGX_STAMP_ARRIVED(2);
 
     // ---- update_states + controller (position_control.py:20-51)
     const float a = clamp_minmax(a_in, -10.0f, 10.0f);  // clip_actions
@@ -2226,11 +2342,13 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
       reset = (crashed && T.reset_on_collision) || trunc;
     }
   }
+  AGX_STAMP(3);
   if (MODE == AGX_STEP_ANY) {  // the hand-off to the helper wave: every lane of every env workgroup, whatever `valid` says
     H->p[tid] = p; H->q[tid] = q; H->v[tid] = v; H->w[tid] = w;
     H->reset[tid] = reset ? 1 : 0;
     __syncthreads();
   }
+  AGX_STAMP(4);
   if (valid) {
     // ---- the position task's reward
     float rew = 0.0f;
@@ -2305,18 +2423,23 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
     atomicOr(B.reset_flag + B.flag_parity, 1);
     if (MODE == AGX_STEP_NONE) atomicAdd(T.proof_violation, 1u);  // cannot happen (the host proved it): tests watch this word
   }
-  if (proof) proof_store_slot(T, B, wb, (int)gridDim.x - 1, reset, horizon, steps, proof_dist, proof_speed);
+  if (proof) proof_store_slot(T, B, wb, env_blocks, reset, horizon, steps, proof_dist, proof_speed);
   if (!FUSED) {
-    if (wb == 0) push_wait_finish(B, push_peek);
+    if (__builtin_expect(push, false)) push_wait_finish(B0, push_peek);
+    AGX_STAMP(5); AGX_STAMP(7);
     return;
   }
-  if (MODE == AGX_STEP_ANY) return;  // the reset, the refresh and the observation are the helper wave's
+  if (MODE == AGX_STEP_ANY) {  // the reset, the refresh and the observation are the helper wave's
+    AGX_STAMP(5); AGX_STAMP(7);
+    return;
+  }
   if (valid) {  // position_setpoint_task.py:194-203: target - p | q | v_body | w_body
     float *o = obs + (size_t)i * 13;
     const float e = tgt - p;
     if (l < 3) { o[l] = e; o[7 + l] = vbody; o[10 + l] = wbody; }
     o[3 + l] = q;
   }
+  AGX_STAMP(5); AGX_STAMP(7);
 }
 
 // The helper wave (wave 1) of an env workgroup of k_position_step_fused<AGX_STEP_ANY>: what k_reset_masked_quad_obs does with
@@ -2329,8 +2452,26 @@ AGX_DEV void position_step_quad(const AgxRobotParams &P, const AgxEnvBuffers &B,
 // Every address stored here belongs to a resetting env (the step wave skips those: `own`) or is a derived tensor / the
 // observation (the step wave writes neither in ANY).  Draws are keyed by (seed, global env, episode, stream, block): evaluating
 // them for the truncating and the crashing envs in two calls gives the same values as one call for both.
-AGX_DEV void position_step_helper(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxTaskArgs &T, const AgxResetArgs &R,
-                                  float *__restrict__ obs, const StepHandoff *H) {
+AGX_DEV void position_step_helper(const AgxRobotParams &P0, const AgxEnvBuffers &B0, int n, const AgxTaskArgs &T0, const AgxResetArgs &R0,
+                                  float *obs, const StepHandoff *H) {
+  AGX_STAMP(0); AGX_STAMP(6);
+  // ---- kernel arguments: every field this wave uses, one batch (arg_pin) -- the reset ranges included: behind the barrier this
+  // wave is the launch's critical path, and a crash's values and every store of a resetting env otherwise start with a fetch
+  AgxRobotParams P = P0;
+  AgxEnvBuffers B = B0;
+  AgxTaskArgs T = T0;
+  AgxResetArgs R = R0;
+#define AGX_HELPER_WAVE_ARGS(X, XN)                                                                                                  \
+  X(B, sim_steps) X(B, episode_count) X(B, env_index_base) X(B, bounds_min) X(B, bounds_max) X(B, state) X(B, derived) X(B, gains)    \
+  X(B, motor_tau_inc) X(B, motor_tau_dec) X(B, motor_thrust) X(B, motor_kT)                                                           \
+  X(P, use_rps) X(P, min_thrust) X(P, max_thrust) X(T, kind) X(T, episode_len) X(T, target) X(T, proof_slots)                         \
+  XN(R, lower_bound_min, 3) XN(R, lower_bound_max, 3) XN(R, upper_bound_min, 3) XN(R, upper_bound_max, 3) XN(R, min_state, 13)        \
+  XN(R, max_state, 13) XN(R, gains_min, 12) XN(R, gains_max, 12) X(R, tau_inc_min) X(R, tau_inc_max) X(R, tau_dec_min)                \
+  X(R, tau_dec_max) X(R, kT_min) X(R, kT_max) X(R, randomize_gains) X(R, seed)
+  AGX_HELPER_WAVE_ARGS(AGX_ARG_READ, AGX_ARG_READ_N)
+  arg_pin(n); arg_pin(obs);
+  AGX_HELPER_WAVE_ARGS(AGX_ARG_PIN, AGX_ARG_PIN_N)
+#undef AGX_HELPER_WAVE_ARGS
   const bool proof = T.proof_slots != nullptr;
   if (proof && blockIdx.x == 0) return;  // the folding workgroup: wave 0's, and no barrier in it
   const int lane = (int)(threadIdx.x & 63u);
@@ -2341,11 +2482,13 @@ AGX_DEV void position_step_helper(const AgxRobotParams &P, const AgxEnvBuffers &
   const bool valid = i < n;
   int steps_in = 0, ep = 0;
   float tgt = 0.0f;
+  AGX_STAMP(1);
   if (valid) {
     steps_in = B.sim_steps[i];
     if (B.episode_count) ep = B.episode_count[i];  // (the reset's draws are keyed by it)
     tgt = T.kind == AGX_TASK_POSITION ? AGX_QAT(T.target, 0, ol3) : 0.0f;
   }
+  AGX_STAMP_ARRIVED(2);
   // ---- phase 1: the step wave's own truncation predicate
   const bool early = valid && T.kind == AGX_TASK_POSITION && steps_in + 1 > T.episode_len;
   ResetValues<4> V{};
@@ -2354,7 +2497,9 @@ AGX_DEV void position_step_helper(const AgxRobotParams &P, const AgxEnvBuffers &
     wave_reset_draws<4>(R, B.env_index_base + i, ep, early && l == 0, D);  // draws are keyed by the GLOBAL env index
     V = reset_env_values<4>(P, R, D);
   }
+  AGX_STAMP(3);
   __syncthreads();
+  AGX_STAMP(4);
   // ---- phase 2
   float p = H->p[lane], q = H->q[lane], v = H->v[lane], w = H->w[lane];
   const bool mine = H->reset[lane] != 0;
@@ -2391,6 +2536,7 @@ AGX_DEV void position_step_helper(const AgxRobotParams &P, const AgxEnvBuffers &
     if (l < 3) { o[l] = e; o[7 + l] = d2.vbody; o[10 + l] = d2.wbody; }
     o[3 + l] = q;
   }
+  AGX_STAMP(5); AGX_STAMP(7);
 }
 
 __global__ void __launch_bounds__(64, 1)
@@ -2414,6 +2560,16 @@ __global__ void __launch_bounds__(MODE == AGX_STEP_ANY ? 128 : 64, 1)
     position_step_quad<MODE>(P, B, n, actions_in, T, obs, nullptr);
   }
 }
+
+#ifdef AGX_STEP_STAMPS
+}  // namespace agx
+// [blocks][2 waves][8] of the LAST position-step launch (blocks <= 1024); a wave that did not run leaves its words as they were
+extern "C" int agx_debug_step_stamps(unsigned long long *out, int blocks) {
+  if (blocks < 0 || blocks > agx::kStampBlocks) return -1;
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(agx::g_step_stamps), sizeof(unsigned long long) * 2 * agx::kStampWords * (size_t)blocks);
+}
+namespace agx {
+#endif
 
 // AssetManager.reset_idx (asset_manager.py:51-71) + the half-obstacle resample (env_manager.py:283-295)
 __global__ void __launch_bounds__(256) k_reset_assets(AgxEnvBuffers B, int n, int K, AgxResetArgs R, const float *__restrict__ u1,

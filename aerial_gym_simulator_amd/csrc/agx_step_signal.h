@@ -23,8 +23,11 @@ namespace agx {
 
 // the env-step index of this launch: a kernel argument (eager stepping) or, when the step is replayed from a hipGraph
 // whose kernel arguments are frozen, a word in device memory that the graph's last node advances
+// (an atomic load, relaxed and of the narrowest scope: an ordinary global load, but one the compiler does not merge with the
+// argument's into a single FLAT load through a selected address -- flat loads also count on lgkmcnt)
 __device__ __forceinline__ int step_index(const AgxEnvBuffers &B) {
-  return B.step_counter_dev ? *B.step_counter_dev : B.step_counter;
+  if (B.step_counter_dev) return __hip_atomic_load(B.step_counter_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  return B.step_counter;
 }
 
 // Stores into ANOTHER device's memory (a peer's receive buffer, mapped through HIP IPC and reached over xGMI): system scope,

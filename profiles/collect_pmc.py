@@ -134,5 +134,32 @@ def main(fetch_csv, write_csv, sq_csv=None, build_id=None, sq2_csv=None, sq3_csv
     print(json.dumps(out, indent=1))
 
 
+STEP_COUNTERS = ("SQ_WAIT_ANY", "SQ_WAVE_CYCLES", "SQ_ACTIVE_INST_ANY", "SQ_INSTS_SMEM", "SQ_INSTS_VALU", "SQ_WAVES")
+
+
+def step_counters(*csvs, kernel="k_position_step_fused<1>"):
+    """The single-launch position step's own counter pass (profiles/step_phase_probe.py --workload under rocprofv3 --pmc, no
+    tracing in the run; the counters may be spread over several passes): per launch of `kernel`, the average of each counter and
+    the share of wave cycles a wave spent parked (SQ_WAIT_ANY / SQ_WAVE_CYCLES).
+
+        python profiles/collect_pmc.py --step-counters pass1/p_counter_collection.csv [pass2/...csv]"""
+    acc = defaultdict(list)
+    for path in csvs:
+        for r in csv.DictReader(open(path)):
+            if kernel in r["Kernel_Name"].replace(" ", "") and r["Counter_Name"] in STEP_COUNTERS:
+                acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
+    out = {"kernel": kernel, "launches": {k: len(v) for k, v in acc.items()}, "per_launch": {k: sum(v) / len(v) for k, v in acc.items()}}
+    d = out["per_launch"]
+    if d.get("SQ_WAVE_CYCLES"):
+        for name in ("SQ_WAIT_ANY", "SQ_ACTIVE_INST_ANY"):
+            if name in d:
+                out[name + "_over_SQ_WAVE_CYCLES"] = d[name] / d["SQ_WAVE_CYCLES"]
+    print(json.dumps(out, indent=1))
+    return out
+
+
 if __name__ == "__main__":
-    main(*sys.argv[1:8])
+    if len(sys.argv) > 1 and sys.argv[1] == "--step-counters":
+        step_counters(*sys.argv[2:])
+    else:
+        main(*sys.argv[1:8])
