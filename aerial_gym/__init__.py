@@ -27,6 +27,8 @@ _ALIAS, _REAL = __name__, _impl.__name__
 # for their class (`task_config`, `control`), mapped below to the class that file defines.
 _FILE_EXPORTS = {
     "task_config.position_setpoint_task_config": {"task_config": "position_setpoint_task_config"},
+    "task_config.position_setpoint_task_sim2real_config": {"task_config": "position_setpoint_task_sim2real_config"},
+    "task_config.position_setpoint_task_acceleration_sim2real_config": {"task_config": "position_setpoint_task_acceleration_sim2real_config"},
     "task_config.navigation_task_config": {"task_config": "navigation_task_config"},
     "task_config.lidar_navigation_task_config": {"task_config": "lidar_navigation_task_config"},
     "controller_config.lee_controller_config": {"control": "lee_controller_config"},
@@ -91,7 +93,9 @@ class _ConfigGroupModule(types.ModuleType):
     same name that lives there"""
 
     def __setattr__(self, name, value):
-        if isinstance(value, _ConfigFileModule) and name in self.__dict__:
+        # (by class name: after `aerial_gym` has been dropped from sys.modules and imported again, the per-file modules are
+        # instances of the NEW import's class while this group module keeps the class it was given first)
+        if type(value).__name__ == "_ConfigFileModule" and name in self.__dict__:
             return
         super().__setattr__(name, value)
 

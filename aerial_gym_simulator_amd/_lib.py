@@ -162,6 +162,7 @@ class AgxTaskArgs(C.Structure):
 
 
 TASK_NONE, TASK_POSITION, TASK_NAVIGATION = 0, 1, 2
+SIM2REAL_VELOCITY, SIM2REAL_ACCELERATION = 0, 1  # `kind` of the agx_sim2real_* entry points
 
 
 class AgxNavRobotSideArgs(C.Structure):
@@ -278,7 +279,7 @@ class AgxLinkFrames(C.Structure):
     _fields_ = [("num_bodies", C.c_int32), ("reserved", C.c_int32), ("rot", (C.c_float * 9) * MAX_BODIES), ("pos", (C.c_float * 3) * MAX_BODIES)]
 
 
-ABI_VERSION = 14  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 15  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -379,6 +380,9 @@ _SIGNATURES = {
     "agx_image_min": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
     "agx_step_counter_advance": (C.c_int, [C.POINTER(AgxEnvBuffers), _P]),
     "agx_reset_set": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, _P]),
+    "agx_sim2real_pre_step": (C.c_int, [C.c_int, C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "agx_sim2real_reward": (C.c_int, [C.c_int, C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "agx_sim2real_obs": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P]),
     "agx_nav_bookkeeping": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "agx_nav_target_reset": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P,
                                        C.c_int, _P]),

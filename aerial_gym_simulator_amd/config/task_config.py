@@ -21,6 +21,34 @@ class position_setpoint_task_config:
     reward_parameters = {}  # the reference's table is unused by its compute_reward (hard-coded constants)
 
 
+class position_setpoint_task_sim2real_config:  # position_setpoint_task_sim2real_config.py:4-23
+    seed = 1
+    sim_name = "base_sim"
+    env_name = "empty_env"
+    robot_name = "lmf2"
+    controller_name = "lmf2_velocity_control"
+    # LMF2Cfg keeps enable_camera = True and the task builds with use_warp = False: the reference would create a rasteriser
+    # camera that these tasks never read.  Opt-in: no camera / LiDAR is created.
+    args = {"ray_cast_sensors": "off"}
+    num_envs = 16
+    use_warp = False
+    headless = False
+    device = "cuda:0"
+    observation_space_dim = 17
+    privileged_observation_space_dim = 0
+    action_space_dim = 4
+    episode_len_steps = 800
+    return_state_before_reset = False
+    reward_parameters = {}
+
+
+class position_setpoint_task_acceleration_sim2real_config(position_setpoint_task_sim2real_config):
+    # position_setpoint_task_acceleration_sim2real_config.py:4-23: the same values, the acceleration controller
+    controller_name = "lmf2_acceleration_control"
+    args = {"ray_cast_sensors": "off"}
+    reward_parameters = {}
+
+
 class navigation_task_config:
     seed = -1
     sim_name = "base_sim"

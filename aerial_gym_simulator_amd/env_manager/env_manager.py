@@ -137,7 +137,8 @@ class EnvManager(BaseManager):
                                   box_objects=bool(self.env_args.get("bvh_box_objects", True)))
         self.keep_in_env = self.scene.keep_in_env_num
         g["num_obstacles_in_env"] = self.scene.num_assets
-        self.robot_manager = RobotManagerHIP(self.global_tensor_dict, self.cfg, self.robot_name, self.controller_name, dev)
+        self.robot_manager = RobotManagerHIP(self.global_tensor_dict, self.cfg, self.robot_name, self.controller_name, dev,
+                                             ray_cast_sensors=self.env_args.get("ray_cast_sensors", "on"))
 
     def prepare_sim(self):
         g = self.global_tensor_dict

@@ -11,7 +11,7 @@ logger = CustomLogger("robot_manager")
 
 
 class RobotManagerHIP:
-    def __init__(self, global_tensor_dict, env_config, robot_name, controller_name, device):
+    def __init__(self, global_tensor_dict, env_config, robot_name, controller_name, device, ray_cast_sensors="on"):
         self.env_config, self.device = env_config, device
         self.num_envs = env_config.env.num_envs
         self.use_warp = env_config.env.use_warp
@@ -19,7 +19,12 @@ class RobotManagerHIP:
         sc = self.cfg.sensor_config
         if sc.enable_camera and sc.enable_lidar:
             raise ValueError("Both camera and lidar are enabled; they share the same image tensors (robot_manager.py:66-90)")
-        if (sc.enable_camera or sc.enable_lidar) and not self.use_warp:
+        if ray_cast_sensors not in ("on", "off"):
+            raise ValueError(f"ray_cast_sensors must be 'on' or 'off' (got {ray_cast_sensors!r})")
+        # "off" (EnvManager args={"ray_cast_sensors": "off"}, opt-in): no camera / LiDAR is created whatever the robot config
+        # enables -- for tasks that never read the image, where the reference would create a rasteriser camera
+        self.ray_cast_sensors = ray_cast_sensors == "on"
+        if (sc.enable_camera or sc.enable_lidar) and not self.use_warp and self.ray_cast_sensors:
             raise ValueError("ray-cast sensors need use_warp=True (the rasteriser camera of Isaac Gym is out of scope)")
         self.warp_sensor = None
         self.imu_sensor = None
@@ -49,7 +54,7 @@ class RobotManagerHIP:
         g["robot_inertia"] = g["robot_inertia"] if "robot_inertia" in g else torch.tensor(pd["inertia"], device=dev).view(1, 3, 3).expand(N, 3, 3)
         self.robot_masses, self.robot_inertias = g["robot_mass"], g["robot_inertia"]
         sc = self.cfg.sensor_config
-        if self.use_warp and (sc.enable_camera or sc.enable_lidar):
+        if self.ray_cast_sensors and self.use_warp and (sc.enable_camera or sc.enable_lidar):
             from ..sensors.hip_sensor import HipSensor
 
             cfg = sc.camera_config if sc.enable_camera else sc.lidar_config

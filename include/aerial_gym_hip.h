@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 14
+#define AGX_ABI_VERSION 15
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -418,6 +418,39 @@ int agx_step_counter_advance(const AgxEnvBuffers *buf, void *stream);
  * set-point of BASELINE configs[3] ([N][7]).  A user-supplied function (any other callable in the config) stays torch.   */
 enum { AGX_ACTION_NAV_VELOCITY = 1, AGX_ACTION_LIDAR_ACCELERATION = 2, AGX_ACTION_FULLY_ACTUATED_POSE = 3 };
 int agx_action_transform(int kind, int num_envs, const float *actions_in, float *out, void *stream);
+
+/* ---- the lmf2 sim2real set-point tasks (position_setpoint_task_sim2real.py, position_setpoint_task_acceleration_sim2real.py) ----
+ * Three launches of one lane per env around the env step.  target: [3][N]; the action tensors are [N][4] row-major and
+ * 16-byte aligned (`actions` IS the tensor the caller handed to task.step()); the vehicle-frame tensors are read and written
+ * by the acceleration kind only (NULL otherwise).
+ *
+ * agx_sim2real_pre_step: step() up to sim_env.step (velocity :157-161, acceleration :161-170), in that order:
+ *   prev_actions <- actions_before (what task.actions reads at the time of the call: the previous call's tensor, possibly
+ *   overwritten by the caller since, possibly `actions` itself), prev_dist <- |target - robot_position| on the pre-step
+ *   position; acceleration kind: prev_actions_vehicle_frame[0:3] <- quat_rotate(robot_orientation, prev_actions[0:3]),
+ *   [3] copied (:162-165), then actions[:, 0:3] *= 2 in place (:170).                                                        */
+enum { AGX_SIM2REAL_VELOCITY = 0, AGX_SIM2REAL_ACCELERATION = 1 };
+int agx_sim2real_pre_step(int kind, const AgxEnvBuffers *buf, int num_envs, const float *target, const float *actions_before,
+                          float *actions, float *prev_actions, float *prev_dist, float *prev_actions_vehicle_frame,
+                          void *stream);
+
+/* compute_rewards_and_crashes + compute_reward (velocity :230-259,286-339; acceleration :239-273,300-356: different constants)
+ * and `truncations = sim_steps > episode_len` (:180-182 / :189-191).  Reads buf->state and the derived tensors as the env
+ * step left them; writes reward[N], actions_vehicle_frame (acceleration: quat_rotate(robot_vehicle_orientation, actions[0:3])),
+ * ORs `dist > 10` into crashes, reward = -50 where crashed, and leaves reset_mask / reset_flag[flag_parity] exactly as
+ * agx_reward_position does (env_manager.py:364-371).                                                                         */
+int agx_sim2real_reward(int kind, const AgxEnvBuffers *buf, int num_envs, const float *target, const float *actions,
+                        const float *prev_actions, const float *prev_dist, float *actions_vehicle_frame,
+                        const float *prev_actions_vehicle_frame, int episode_len, int reset_on_collision, float *reward,
+                        void *stream);
+
+/* process_obs_for_task (:202-228 / :211-237, identical in both tasks): obs [N][17] row-major = position error + 0.03 z_p |
+ * quat_from_euler_xyz(ssa(euler_xyz(q)) + 0.02 z_e) | body linvel + 0.02 z_v | body angvel + 0.02 z_w | robot_actions, where
+ * q = sign(w) * robot_orientation is STORED BACK into buf->state like the reference's in-place write (:204-207; sign is 0 at
+ * +-0).  noise: standard normals [4][N][3] in the reference's randn_like order (euler, position, linvel, angvel).  Exchange
+ * rows (buf->step_rows) are not written for this observation: the call refuses them.                                       */
+int agx_sim2real_obs(const AgxEnvBuffers *buf, int num_envs, const float *target, const float *noise, float *obs,
+                     void *stream);
 
 /* The reset set of EnvManager.reset_terminated_and_truncated_envs (env_manager.py:364-371) from the flags as they are:
  * reset_mask = crashes * reset_on_collision | truncations, reset_flag[flag_parity] |= any.  For callers that did not
