@@ -10,6 +10,10 @@ What is pinned by these vectors (everything that exists as source in the referen
                            with the algorithm of robots/robot_manager.py:295-435 (row a26)
   step_<robot>_<ctrl>.npz  BaseMultirotor.step = update_states + controller + allocation +
                            motor model + drag + disturbance, K chained sub-steps (rows a1-a14)
+  step_edge_<robot>_<ctrl>.npz  the same ten cases on the edge table (EdgeSource: 96 envs x 2 sub-steps; every attitude incl. the
+                           special cases of get_euler_xyz / atan2 / the angle wraps, velocities and actions beyond their clamps,
+                           motor thrusts at their limits and negative, the four branches of matrix_to_quaternion, f = 0 and
+                           f below the horizon); the generator asserts that the reference stays finite on it
   reward_position.npz      position_setpoint_task.compute_reward (row a17)
   reward_navigation.npz    navigation_task.compute_reward (row a18)
   trace_position_64.npz    BASELINE config 1: 64 envs, empty_env, reference control + reference
@@ -259,7 +263,188 @@ def gains(robot, n):
     return (z, z, z, z)
 
 
-def gen_step(robot_name, robot_cfg, controller_name, ctrl_key, consts, n=64, K=6, seed=7, action_scale=1.0):
+class NominalSource:
+    """states and actions of the ordinary step fixtures: nominal flight (tilt <= 0.6 rad about each of roll and pitch)"""
+    prefix = "step_"
+
+    def __init__(self, action_scale=1.0):
+        self.action_scale = action_scale
+
+    def initial(self, c):
+        return random_state(c.n, c.rng), None  # the motor thrusts stay what the reference's reset drew
+
+    def action(self, c, k):
+        if c.ctrl_key == "no_control":
+            return torch.rand(c.n, c.A, generator=c.rng) * 2.5 - 0.2
+        if c.ctrl_key == "fully_actuated":
+            return torch.cat([(torch.rand(c.n, 3, generator=c.rng) - 0.5) * 2, torch.randn(c.n, 4, generator=c.rng)], dim=1)
+        action = (torch.rand(c.n, c.A, generator=c.rng) - 0.5) * 2 * self.action_scale
+        if k == c.K - 1:
+            action = action * 30.0  # exercise the +-10 clip and the yaw-rate clamp
+        return action
+
+    def check(self, c, out):
+        pass
+
+
+EDGE_SCALES = (0.0, 1.0, 10.0)          # per-env factor of the linear / angular velocity: at rest, nominal, beyond the clamps
+EDGE_ACTION_SCALES = (0.0, 1.0, 30.0)   # per-env factor of the action: zero, nominal, beyond the +-10 clip / the yaw-rate clamp
+LEE_BRANCH_CASES = ("position", "velocity", "velocity_steering")  # controllers that go through matrix_to_quaternion
+EDGE_BRANCH_ROWS = (24, 88)             # envs whose commands are chosen for the four branches of matrix_to_quaternion
+
+
+def edge_quaternions(n, rng):
+    """xyzw, float32: the fixed rows of the edge table (every special case of get_euler_xyz / atan2 / the angle wraps), then
+    quaternions uniform on the sphere"""
+    r = float(np.sqrt(np.float32(0.5)))               # float32(sqrt(1/2)): 2 r r is one ulp under 1
+    r_up = float(np.nextafter(np.float32(r), np.float32(1.0)))  # |q| an ulp above 1: 2 r_up r_up > 1
+    yaw = lambda a: (0.0, 0.0, math.sin(a / 2), math.cos(a / 2))  # noqa: E731
+    roll = lambda a: (math.sin(a / 2), 0.0, 0.0, math.cos(a / 2))  # noqa: E731
+    d = 5e-5
+    rows = [
+        (0, 0, 0, 1), (0, 0, 0, -1),                  # identity, and the same attitude with w < 0
+        (1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0),     # 180 deg about x, y, z
+        (0, r, 0, r), (0, -r, 0, r),                  # +-90 deg pitch: sinp one ulp under 1
+        (0.5, 0.5, -0.5, 0.5), (0.5, -0.5, 0.5, 0.5),  # sinp = +-1 exactly (and atan2(0, 0) for roll and yaw)
+        (0, r_up, 0, r_up),                           # |sinp| > 1
+        (r, 0, 0, r), (0, 0, r, r), (0, 0, -r, r),    # 90 deg roll, +-90 deg yaw
+        yaw(math.pi - d), yaw(math.pi + d), yaw(-math.pi + d), yaw(-math.pi - d),  # yaw either side of +-pi
+        roll(d), roll(-d), roll(math.pi - d), roll(math.pi + d),                    # roll either side of 0 and of pi
+        (r, 0, r, 0),
+        (0.5, 0.5, 0.5, 0.5),                         # cosr_cosp == 0 (and cosy_cosp == 0), sinr_cosp = 1
+        (0.5, -0.5, -0.5, 0.5),                       # cosy_cosp == 0, siny_cosp = -1
+    ]
+    q = torch.tensor(rows, dtype=torch.float32)
+    assert q.shape[0] == EDGE_BRANCH_ROWS[0]
+    rest = torch.nn.functional.normalize(torch.randn(n - q.shape[0], 4, generator=rng), dim=1)
+    return torch.cat([q, rest], dim=0)
+
+
+def lee_branches(state, action, qveh, euler, Kp, Kv, pd, ctrl_key):
+    """which of the four candidates matrix_to_quaternion picks for the desired attitude of the Lee position / velocity laws
+    (base_lee_controller.py: b3 = f / |f|, b2 = b3 x (cos yaw, sin yaw, 0), b1 = b2 x b3), from the recorded inputs in float64"""
+    st, act, qv, Kp, Kv = (np.asarray(x, np.float64) for x in (state, action, qveh, Kp, Kv))
+    pos, v = st[:, 0:3], st[:, 7:10]
+    if ctrl_key == "position":
+        acc, yaw = Kp * (act[:, 0:3] - pos) + Kv * (0.0 - v), act[:, 3]
+    else:
+        u, w, c = qv[:, 0:3], qv[:, 3:4], act[:, 0:3]
+        rot = c * (2.0 * w * w - 1.0) + np.cross(u, c) * w * 2.0 + u * (u * c).sum(1, keepdims=True) * 2.0
+        acc = Kv * (rot - v)
+        yaw = act[:, 3] if ctrl_key == "velocity_steering" else np.asarray(euler, np.float64)[:, 2]
+    f = (acc - np.asarray(pd["gravity"], np.float64)) * pd["mass"]
+    b3 = f / np.linalg.norm(f, axis=1, keepdims=True)
+    b2 = np.cross(b3, np.stack([np.cos(yaw), np.sin(yaw), np.zeros_like(yaw)], axis=1))
+    b2 = b2 / np.linalg.norm(b2, axis=1, keepdims=True)
+    b1 = np.cross(b2, b3)
+    m00, m11, m22 = b1[:, 0], b2[:, 1], b3[:, 2]
+    t = np.stack([1 + m00 + m11 + m22, 1 + m00 - m11 - m22, 1 - m00 + m11 - m22, 1 - m00 - m11 + m22], axis=1)
+    return np.argmax(t, axis=1)
+
+
+class EdgeSource:
+    """The edge table: every attitude (fixed special rows + the whole sphere), velocities at rest / nominal / beyond the clamps,
+    motor thrusts at their limits, at zero and negative, actions at zero / nominal / beyond the clips, and the command rows
+    listed in action()."""
+    prefix = "step_edge_"
+
+    def initial(self, c):
+        n, M, rng = c.n, c.M, c.rng
+        i = torch.arange(n)
+        s = torch.zeros(n, 13)
+        s[:, 0:3] = (torch.rand(n, 3, generator=rng) - 0.5) * 2
+        s[:, 3:7] = edge_quaternions(n, rng)
+        lin = torch.tensor(EDGE_SCALES)[i % 3]
+        ang = torch.tensor(EDGE_SCALES)[(i // 3) % 3]
+        lo, hi = EDGE_BRANCH_ROWS
+        if c.ctrl_key in LEE_BRANCH_CASES:
+            down = (i >= lo) & (i < hi) & (i % 2 == 1)  # the rows whose command puts the thrust force below the horizon: at rest
+            lin = torch.where(down, torch.zeros_like(lin), lin)
+            s[down, 2] = 0.5 + 0.5 * s[down, 2].abs()
+        s[:, 7:10] = (torch.rand(n, 3, generator=rng) - 0.5) * 2 * lin[:, None]
+        s[:, 10:13] = (torch.rand(n, 3, generator=rng) - 0.5) * 2 * ang[:, None]
+        tmin, tmax = c.pd["min_thrust"], c.pd["max_thrust"]
+        u = torch.rand(n, M, generator=rng)
+        anywhere = tmin + (tmax - tmin) * u
+        # octarotor: negative thrusts, near zero (the commanded thrust lies below as often as above) and down to the limit
+        negative = tmin * u * torch.where(torch.arange(M) % 2 == 0, 1.0, 0.02)[None, :] if tmin < 0 else anywhere
+        j = torch.arange(M)[None, :].expand(n, M)
+        mixed = torch.where(j % 4 == 0, torch.full_like(u, tmin), torch.where(j % 4 == 1, torch.full_like(u, tmax),
+                            torch.where(j % 4 == 2, torch.zeros_like(u), anywhere)))
+        pick = (i % 6)[:, None]
+        th = torch.where(pick == 0, torch.full_like(u, tmin), torch.where(pick == 1, torch.full_like(u, tmax),
+                         torch.where(pick == 2, torch.zeros_like(u), torch.where(pick == 3, anywhere,
+                                     torch.where(pick == 4, negative, mixed)))))
+        return s, th
+
+    def action(self, c, k):
+        n, A, rng, key = c.n, c.A, c.rng, c.ctrl_key
+        i = torch.arange(n)
+        st = c.gtd["robot_state_tensor"]
+        if key == "fully_actuated":
+            a = torch.cat([(torch.rand(n, 3, generator=rng) - 0.5) * 2, torch.randn(n, 4, generator=rng)], dim=1)
+        elif key == "no_control":
+            a = torch.rand(n, A, generator=rng) * 2.5 - 0.2
+        else:
+            a = (torch.rand(n, A, generator=rng) - 0.5) * 2
+        a = a * torch.tensor(EDGE_ACTION_SCALES)[(i // 9 + k) % 3][:, None]
+        u = torch.rand(n, 4, generator=rng)
+        if key == "fully_actuated":
+            a[0, 3:7] = 0.0                                         # |q| = 0: the norm's 1e-9 floor
+            a[1, 3:7] = torch.tensor([0.0, 0.0, 0.0, 1e-10])        # |q| below the floor: q / 1e-9
+            a[2, 3:7] = torch.tensor([0.0, 0.0, 0.0, -1.0])
+        elif key == "acceleration":
+            g = -9.81
+            rows = [(0, 0, g), (5, 0, g), (-5, 0, g), (0, 5, g), (0, -5, g), (0, 0, -10), (3, -4, g), (0, 0, 10)]
+            for r, acc in enumerate(rows):  # f = 0 (atan2(0, 0)), f horizontal along each axis, f straight down, ...
+                for rep in range(3):        # ... each on three attitudes (a fixed row, and two of the sphere)
+                    e = r + 32 * rep
+                    a[e, 0:3] = torch.tensor(acc, dtype=torch.float32)
+        elif key in LEE_BRANCH_CASES:
+            lo, hi = EDGE_BRANCH_ROWS
+            rows = (i >= lo) & (i < hi)
+            down = rows & (i % 2 == 1)
+            up = rows & (i % 2 == 0)
+            # yaw set-point (position, velocity_steering: the action's 4th entry; velocity: the vehicle's own yaw, over the sphere):
+            # about 0 -> branches 0 (f up) and 1 (f down), about pi -> 3 (f up) and 2 (f down)
+            about_pi = (i // 2) % 2 == 1
+            yaw = (u[:, 3] - 0.5) * 2.0 + torch.where(about_pi, math.pi, 0.0)
+            if key == "position":
+                # position set-point 10 m below (the clip): K_pos (p_cmd - p) < g; and within 0.5 m: thrust force up
+                a[down, 0:2] = st[down, 0:2] + (u[down, 0:2] - 0.5) * 0.2
+                a[down, 2] = -10.0
+                a[up, 0:3] = st[up, 0:3] + (u[up, 0:3] - 0.5)
+                a[rows, 3] = yaw[rows]
+            else:
+                a[down, 0:2] = (u[down, 0:2] - 0.5) * 2.0
+                a[down, 2] = -10.0
+                a[up, 0:3] = (u[up, 0:3] - 0.5) * 2.0
+                a[rows, 3] = yaw[rows] if key == "velocity_steering" else (u[rows, 3] - 0.5) * 2.0
+        return a
+
+    def check(self, c, out):
+        for name, x in out.items():
+            if x.dtype.kind == "f":
+                assert np.isfinite(x).all(), (c.ctrl_key, name, "the reference is not finite on the edge table")
+        q = out["state"][0][:, 3:7]
+        sinp = np.float32(2.0) * (q[:, 3] * q[:, 1] - q[:, 2] * q[:, 0])  # float32, the reference's expression
+        assert sinp.dtype == np.float32 and sinp[7] == 1.0 and sinp[8] == -1.0 and sinp[9] > 1.0, sinp[5:10]
+        assert sinp[5] == np.nextafter(np.float32(1), np.float32(0)) and sinp[6] == -sinp[5], sinp[5:7]
+        if c.ctrl_key in LEE_BRANCH_CASES:
+            Kp, Kv = out["Kp"], out["Kv"]
+            br = np.concatenate([lee_branches(out["state"][k], out["action_after"][k], out["qveh"][k], out["euler"][k], Kp, Kv,
+                                              c.pd, c.ctrl_key) for k in range(c.K)])
+            counts = np.bincount(br, minlength=4)
+            print(f"  matrix_to_quaternion branches taken: {counts.tolist()}")
+            assert counts.min() >= 8, (c.ctrl_key, counts)
+
+
+class _Ctx:
+    pass
+
+
+def gen_step(robot_name, robot_cfg, controller_name, ctrl_key, consts, n=64, K=6, seed=7, action_scale=1.0, source=None):
+    source = source or NominalSource(action_scale)
     rng = torch.Generator().manual_seed(seed)
     robot, gtd = make_ref_robot(robot_cfg, controller_name, n, consts, seed)
     ctrl_cfg = robot.controller_config
@@ -269,8 +454,13 @@ def gen_step(robot_name, robot_cfg, controller_name, ctrl_key, consts, n=64, K=6
     A = robot.num_actions
     pd = params_dict(robot_cfg, ctrl_cfg, ctrl_key, consts)
     P = orc.make_params(pd)
-    gtd["robot_state_tensor"][:] = random_state(n, rng)
+    c = _Ctx()
+    c.n, c.K, c.M, c.A, c.rng, c.ctrl_key, c.pd, c.gtd = n, K, M, A, rng, ctrl_key, pd, gtd
+    state0, thrust0 = source.initial(c)
+    gtd["robot_state_tensor"][:] = state0
     thrust, kT, tinc, tdec = motor_arrays(robot, n, M)
+    if thrust0 is not None:
+        thrust[:] = thrust0
     Kp, Kv, KR, Kw = gains(robot, n)
     rec = {k: [] for k in ("state", "action", "thrust_in", "thrust_out", "euler", "qveh", "vveh", "vbody", "wbody",
                            "wrench_cmd", "force", "torque", "disturb", "action_after",
@@ -279,14 +469,7 @@ def gen_step(robot_name, robot_cfg, controller_name, ctrl_key, consts, n=64, K=6
     dist_on = bool(robot_cfg.disturbance.enable_disturbance)
     dmax = torch.tensor(robot_cfg.disturbance.max_force_and_torque_disturbance)
     for k in range(K):
-        if ctrl_key == "no_control":
-            action = torch.rand(n, A, generator=rng) * 2.5 - 0.2
-        elif ctrl_key == "fully_actuated":
-            action = torch.cat([(torch.rand(n, 3, generator=rng) - 0.5) * 2, torch.randn(n, 4, generator=rng)], dim=1)
-        else:
-            action = (torch.rand(n, A, generator=rng) - 0.5) * 2 * action_scale
-            if k == K - 1:
-                action = action * 30.0  # exercise the +-10 clip and the yaw-rate clamp
+        action = source.action(c, k)
         rec["state"].append(gtd["robot_state_tensor"].clone())
         rec["action"].append(action.clone())
         rec["thrust_in"].append(thrust.clone())
@@ -331,8 +514,9 @@ def gen_step(robot_name, robot_cfg, controller_name, ctrl_key, consts, n=64, K=6
     out.update(kT=kT.numpy(), tau_inc=tinc.numpy(), tau_dec=tdec.numpy(), Kp=Kp.numpy(), Kv=Kv.numpy(),
                KR=KR.numpy(), Kw=Kw.numpy(), disturb_max=dmax.numpy(), application_mask=mask.numpy(),
                params_json=np.array(json.dumps(pd)))
-    np.savez(os.path.join(OUT, f"step_{robot_name}_{ctrl_key}.npz"), **out)
-    print(f"step_{robot_name}_{ctrl_key}: ok  wrench[0]={out['wrench_cmd'][0, 0]}")
+    source.check(c, out)
+    np.savez(os.path.join(OUT, f"{source.prefix}{robot_name}_{ctrl_key}.npz"), **out)
+    print(f"{source.prefix}{robot_name}_{ctrl_key}: ok  wrench[0]={out['wrench_cmd'][0, 0]}")
 
 
 # --------------------------------------------------------------------------------------
@@ -540,6 +724,18 @@ def register_unregistered_reference_controllers():
     controller_registry.register_controller("lee_rates_control_zfix", LeeRatesControllerZ, ctrl.lee_controller_config)
 
 
+STEP_CASES = (  # robot, robot config, controller in the reference's registry, controller key, action scale of the nominal fixture
+    ("quad", "quad", "lee_position_control", "position", 1.0), ("quad", "quad", "lee_velocity_control", "velocity", 1.0),
+    ("quad", "quad", "lee_attitude_control", "attitude", 1.0), ("quad", "quad", "lee_acceleration_control", "acceleration", 1.0),
+    ("quad", "quad", "no_control", "no_control", 1.0),
+    ("octarotor", "octarotor", "octarotor_position_control", "position", 1.0),
+    ("octarotor", "octarotor", "octarotor_velocity_control", "velocity", 1.0),
+    ("octarotor", "octarotor", "rov_fully_actuated_control", "fully_actuated", 1.0),
+    ("quad", "quad", "lee_velocity_steering_angle_control", "velocity_steering", 1.0),
+    ("quad", "quad", "lee_rates_control_zfix", "rates", 2.0),
+)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     rng = torch.Generator().manual_seed(2024)
@@ -554,16 +750,14 @@ def main():
             np.savez(os.path.join(OUT, f"robot_{name}.npz"), **c)
         print(name, "mass", c["mass"], "J diag", np.diag(c["inertia"]), "com", c["com"],
               "| max |W - A| =", np.abs(c["wrench_map"] - c["alloc"]).max())
-    for ctrl_name, key in (("lee_position_control", "position"), ("lee_velocity_control", "velocity"),
-                           ("lee_attitude_control", "attitude"), ("lee_acceleration_control", "acceleration"),
-                           ("no_control", "no_control")):
-        gen_step("quad", BaseQuadCfg, ctrl_name, key, consts["quad"])
-    for ctrl_name, key in (("octarotor_position_control", "position"), ("octarotor_velocity_control", "velocity"),
-                           ("rov_fully_actuated_control", "fully_actuated")):
-        gen_step("octarotor", BaseOctarotorCfg, ctrl_name, key, consts["octarotor"])
     register_unregistered_reference_controllers()
-    gen_step("quad", BaseQuadCfg, "lee_velocity_steering_angle_control", "velocity_steering", consts["quad"])
-    gen_step("quad", BaseQuadCfg, "lee_rates_control_zfix", "rates", consts["quad"], action_scale=2.0)
+    for robot_name, robot_cfg, ctrl_name, key, scale in STEP_CASES:
+        cfg = {"quad": BaseQuadCfg, "octarotor": BaseOctarotorCfg}[robot_cfg]
+        gen_step(robot_name, cfg, ctrl_name, key, consts[robot_name], action_scale=scale)
+    for robot_name, robot_cfg, ctrl_name, key, scale in STEP_CASES:
+        # the same ten cases on the edge table (EdgeSource): all attitudes, controller edge inputs
+        cfg = {"quad": BaseQuadCfg, "octarotor": BaseOctarotorCfg}[robot_cfg]
+        gen_step(robot_name, cfg, ctrl_name, key, consts[robot_name], n=96, K=2, seed=11, source=EdgeSource())
     gen_rewards(rng)
     gen_trace(consts["quad"], "lee_position_control", "position", "position")
     gen_trace(consts["quad"], "lee_attitude_control", "attitude", "attitude", T=160)

@@ -80,6 +80,13 @@ def test_single_substep_vs_oracle_and_golden(orc, parity, case):
     * vs the reference's own outputs (goldens): derived body-frame velocities / vehicle quaternion / Euler angles,
       controller wrench, and the next state (reference control + oracle integrator) within 1e-5 max(1, |x|) per
       component; motor thrusts within 1e-5 of the thrust full scale (2 N quad, 6.25 N octarotor)."""
+    single_substep_vs_oracle_and_golden(orc, parity, case)
+
+
+def single_substep_vs_oracle_and_golden(orc, parity, case, edge=False):
+    """the comparison of test_single_substep_vs_oracle_and_golden on the fixture tests/golden/step_<case>.npz; edge=True (the
+    fixtures of tests/edge_cases_util.py): the gates against the reference's recorded numbers are those of
+    edge_cases_util.gates_vs_reference (the same 1e-5, at most 1 % of an array where the reference's own answer is undefined)"""
     from gpu_harness import DynHarness
 
     g = load_golden("step_" + case)
@@ -103,6 +110,20 @@ def test_single_substep_vs_oracle_and_golden(orc, parity, case):
         H.substeps(g["action"][k], 1)
         gs, gt, gd = H.get("state"), H.get("thrust"), H.get("derived")
         state_gate(parity, f"substep_vs_oracle[{case}]", gs, st, EXACT, ctx=k)
+        if edge:
+            from edge_cases_util import gates_vs_reference
+
+            e, qv, vv, vb, wb = _derived_split(gd)
+            parity.check(f"substep_thrust_vs_oracle[{case}]", max_abs(gt, th), EXACT, "abs (bit-exact)", k)
+            parity.check(f"substep_euler_vs_oracle[{case}]", _angle_err(e, o.euler), EXACT, "rad (bit-exact)", k)
+            for name, got, ref in (("qveh", qv, o.qveh), ("vveh", vv, o.vveh), ("vbody", vb, o.vbody), ("wbody", wb, o.wbody)):
+                parity.check(f"substep_{name}_vs_oracle[{case}]", max_abs(got, ref), EXACT, "abs (bit-exact)", k)
+            if "no_control" not in case:
+                parity.check(f"substep_wrench_vs_oracle[{case}]", max_abs(H.get("wrench"), o.wrench_cmd), EXACT, "abs (bit-exact)", k)
+            gates_vs_reference(parity, "substep", case, g, k, dict(euler=e, qveh=qv, vveh=vv, vbody=vb, wbody=wb, wrench=H.get("wrench"),
+                                                                   thrust=gt, next_state=gs), fs)
+            assert np.array_equal(H.get("actions"), g["action"][k])
+            continue
         if k + 1 < K:  # the generator advanced the reference's wrench with the oracle integrator: state[k + 1]
             state_gate(parity, f"substep_vs_reference_next_state[{case}]", gs, g["state"][k + 1], ctx=k,
                        ref_cr=g["state_next_cr"][k] if "state_next_cr" in g.files else None)

@@ -14,6 +14,7 @@ to the oracle (tests/test_gpu_*.py), hence to these fixtures."""
 import numpy as np
 import pytest
 from conftest import TraceReader, golden_params, load_golden
+from edge_cases_util import EDGE_CASES
 
 STEP_CASES = ["quad_position", "quad_velocity", "quad_attitude", "quad_acceleration", "quad_no_control",
               "octarotor_position", "octarotor_velocity", "octarotor_fully_actuated", "quad_rates", "quad_velocity_steering"]
@@ -41,7 +42,7 @@ def test_math_helpers_bit_exact(orc):
     assert np.array_equal(vbody, g["quat_rotate_inverse"]) and np.array_equal(wbody, g["quat_rotate_inverse"])
 
 
-@pytest.mark.parametrize("case", STEP_CASES)
+@pytest.mark.parametrize("case", STEP_CASES + EDGE_CASES)
 def test_substep_bit_exact(orc, case):
     """BaseMultirotor.step (rows a1-a14) + the oracle integrator: every recorded output, bit for bit."""
     g = load_golden("step_" + case, cr=True)
@@ -70,7 +71,7 @@ def test_substep_bit_exact(orc, case):
             assert np.array_equal(st, g["state"][k + 1]), (case, k)
 
 
-@pytest.mark.parametrize("case", STEP_CASES)
+@pytest.mark.parametrize("case", STEP_CASES + EDGE_CASES)
 def test_substep_on_the_ordinary_fixtures_inputs_bit_exact(orc, case):
     """tests/golden/step_<case>.npz (the reference as torch evaluates it) also carries what the same code returns on the
     same recorded inputs with correctly rounded functions (`*_cr`): the oracle reproduces those bit for bit, and the
