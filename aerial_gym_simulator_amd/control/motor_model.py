@@ -1,7 +1,7 @@
 """Host mirror of aerial_gym/control/motor_model.py: owns the per-env, per-motor tensors
 (thrust state and the randomised first-order-model parameters).  The update itself
 (clamp, time-constant selection, RK4/Euler in thrust or RPM domain) runs inside
-agx_dynamics_substeps (csrc/agx_dynamics.hip: motor_update)."""
+agx_dynamics_substeps (csrc/agx_dyn_physics.h: motor_update)."""
 from ..tensors import aos_view, soa
 
 

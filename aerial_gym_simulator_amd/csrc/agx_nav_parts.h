@@ -1,5 +1,5 @@
 // Per-env pieces of the navigation tasks' reset and sensor-pose path, shared by the stand-alone kernels (agx_task_glue.hip,
-// agx_raycast.hip) and by the ONE launch that runs them behind the robot reset (k_nav_robot_side in agx_dynamics.hip): the same
+// agx_raycast.hip) and by the ONE launch that runs them behind the robot reset (k_nav_robot_side in agx_dyn_reset.h): the same
 // device functions, so the fused launch leaves what the separate launches leave.
 #pragma once
 #include "agx_common.h"

@@ -4,7 +4,7 @@ workload: 8192 envs, Lee position control, episodes desynchronised).
 
     python profiles/step_phase_probe.py --stamps [--lib FILE] [--steps 300] [--out FILE]
         builds (or takes: --lib) the library variant with -DAGX_STEP_STAMPS, in which lane 0 of every wave stamps the shader clock
-        at six points (csrc/agx_dynamics.hip: AGX_STAMP) and the 100 MHz wall clock at its start and end, runs the steps one by
+        at six points (csrc/agx_dyn_position_step.h: AGX_STAMP) and the 100 MHz wall clock at its start and end, runs the steps one by
         one and reports, per phase, the median over the waves and the wave that finished LAST, each as the median over the ANY
         launches; and how often the folding workgroup 0 was that last finisher
     python profiles/step_phase_probe.py --workload [--steps 300]

@@ -1,7 +1,7 @@
 """CPU: how the position-step kernels fetch their kernel arguments and inputs, read from the gfx950 code object (no GPU needed).
 
 A wave of these kernels runs alone on its SIMD, so every `s_waitcnt lgkmcnt(0)` behind an s_load is a scalar-memory round trip it
-sits out.  Each wave therefore fetches every argument field it uses as one batch at its top (csrc/agx_dynamics.hip: arg_pin) and
+sits out.  Each wave therefore fetches every argument field it uses as one batch at its top (csrc/agx_dyn_state.h: arg_pin) and
 issues every input load before it waits for any; no access goes through a FLAT instruction, which counts on lgkmcnt as well as on
 vmcnt.  The caps on the AGX_STEP_ANY instance are set against the parent of this change: 100 s_load and
 82 `s_waitcnt lgkmcnt(0)` in its body (the LDS waits at the hand-off included, then as now)."""

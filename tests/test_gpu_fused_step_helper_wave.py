@@ -1,4 +1,4 @@
-"""GPU: k_position_step_fused<AGX_STEP_ANY> with its helper wave (csrc/agx_dynamics.hip) against the two
+"""GPU: k_position_step_fused<AGX_STEP_ANY> with its helper wave (csrc/agx_dyn_position_step.h) against the two
 launches it replaces.
 
 In an ANY launch the step wave of a workgroup integrates its 16 envs while the helper wave evaluates the draws and the new state

@@ -1,4 +1,4 @@
-"""GPU: single-launch position steps (include/aerial_gym_hip.h AgxPositionStepPlan.proof_*, csrc/agx_dynamics.hip
+"""GPU: single-launch position steps (include/aerial_gym_hip.h AgxPositionStepPlan.proof_*, csrc/agx_dyn_position_step.h
 k_position_step_fused) against the two launches they replace.
 
 A task with args={"single_launch_step": False} always issues the two launches; its twin, same seed, issues a step as ONE launch

@@ -1,7 +1,7 @@
 """GPU: the position step under every shape of arguments its load block branches on, three ways.
 
 The step wave and the helper wave of the position-step kernels fetch their kernel arguments as one batch and issue their input
-loads as one batch (csrc/agx_dynamics.hip: arg_pin, position_step_quad, position_step_helper).  What the
+loads as one batch (csrc/agx_dyn_state.h: arg_pin; agx_dyn_position_step.h: position_step_quad, position_step_helper).  What the
 batch holds depends on which optional buffers exist: per-env controller gains or the uniform ones, per-motor time constants or
 the uniform ones, the thrust constant with use_rps, the body-force and wrench outputs, and whether a crash resets an env.  For
 each shape, a single-launch task (ANY / NONE launches), its two-launch twin and the CPU oracle's env loop run 60 steps on the
