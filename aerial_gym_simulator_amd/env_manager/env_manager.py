@@ -1,14 +1,19 @@
 """EnvManager: same orchestration API as aerial_gym/env_manager/env_manager.py, driving the
 HIP library instead of Isaac Gym + Warp + torch op chains.
 
-Per env step (`step` + the task's reward + `post_reward_calculation_step`) the launches are
-    agx_dynamics_substeps   k sub-steps: controller .. integration .. collision   (1 kernel)
-    agx_reward_*            task reward, crash / truncation flags, reset set       (1 kernel)
-    agx_reset_masked        reset sampling + derived-state refresh                  (1 kernel)
-    [scene + BVH rebuild of reset envs, sensor pose, ray-cast, post-processing]
-    agx_obs_*               observation packing                                     (1 kernel)
-all stream-ordered on torch's current stream, with no host synchronisation unless the
-caller asks for the reset set as indices or `strict_rng` is requested.
+Which launches make one `task.step()` is DESIGN.md section 1 (position task: one or two, in one host call; navigation: six;
+sim2real: six).  All are stream-ordered on torch's current stream, looked up at every launch, with no host synchronisation
+unless the caller asks for the reset set as indices or `strict_rng` is requested.
+
+The EnvManager owns the host state of a step, and nobody else assigns it:
+    flag_parity    which word of the double-buffered reset flag this step uses (AgxEnvBuffers; `_parity` reads it)
+    step_counter   env steps so far, and its copy B.step_counter, the counter word of the step's device RNG streams
+    the record     what this step's launches have ALREADY produced (REWARD, RESET_SET, OBSERVATION, SENSOR_POSES, TARGETS):
+                   a fused launch marks what it did on the side (`mark_produced`), the method that would launch the same work
+                   takes the entry and skips once (`take_produced`; `has_produced` only looks)
+`_begin_call()` empties the record at the top of every public entry that changes state, so no entry outlives the state it
+describes; `_begin_step()` / `_end_step()` are the step advance that EnvManager.step, the position task's one-call step and
+the navigation task's graph replay share.
 """
 import math
 
@@ -77,13 +82,13 @@ class EnvManager(BaseManager):
         self.random_source = self.env_args.get("random_source") or TorchRandomSource(device)
         # seed of the device-side counter RNG used by the sync-free mode (Philox4x32-10)
         self.rng_seed = int(self.env_args.get("rng_seed", torch.initial_seed())) & 0xFFFFFFFFFFFFFFFF
-        self._parity = 0
+        self._buffers = None
+        self._produced = set()  # the record: what this step's launches have already produced
         self.task_args = None   # AgxTaskArgs: reward / flags fused into the env-step launch
         self.post_obs = None    # (target_ptr, obs_ptr): observation fused into the reset launch
         self.global_tensor_dict = TensorDict()
         self.keep_in_env = None
         self.step_counter = 0
-        self._stream_cache = None
         self._step_counter_dev = None
         self._lib = None
         self.populate_env(env_cfg=self.cfg, sim_cfg=self.sim_config)
@@ -154,9 +159,7 @@ class EnvManager(BaseManager):
         """Collect raw device pointers once: tensors are allocated once and never re-allocated."""
         g, robot = self.global_tensor_dict, self.robot_manager.robot
         if torch.device(self.device).type != "cuda":
-            # tensors can be inspected on the CPU (host-logic tests), stepping cannot
-            self._buffers = None
-            return
+            return  # tensors can be inspected on the CPU (host-logic tests), stepping cannot: no buffers
         mm = robot.control_allocator.motor_model
         B = AgxEnvBuffers()
         p = _lib.dptr
@@ -185,7 +188,6 @@ class EnvManager(BaseManager):
         B.wrench_cmd = None  # only the stand-alone controller call stores the wrench
         B.crashes, B.truncations = p(g["crashes"]), p(g["truncations"])
         B.sim_steps, B.reset_mask, B.reset_flag = p(g["sim_steps"]), p(g["reset_mask"]), p(g["reset_flag"])
-        B.flag_parity = self._parity
         B.episode_count = p(g["episode_count"])
         B.bounds_min, B.bounds_max = p(self.bounds_soa[0]), p(self.bounds_soa[1])
         B.disturb = None
@@ -206,7 +208,6 @@ class EnvManager(BaseManager):
         robot.controller._env_binding = self
         self._make_reset_args()
         self._disturb_buf = None
-        self._reward_fresh = self._obs_fresh = self._mask_fresh = False
         if (self.env_args.get("lean_step") and self.num_envs >= self.LEAN_MIN_ENVS and self._params.controller != 8  # 8: external controller
                 and not getattr(robot, "external_robot", False)):
             self._enable_lean_step()
@@ -276,7 +277,7 @@ class EnvManager(BaseManager):
         """recv_ptrs / flag_ptrs: the addresses IN THIS PROCESS of every rank's receive buffer [slots][world][N][row_len] and
         flag array [slots][world] (agx_exchange_push_peers).  From now on every step's rows are stored by the row-writing
         kernels into slot (seq - 1) % slots of EVERY rank's buffer (AgxEnvBuffers.push_*): no launch and no host call per
-        step for the exchange; `_advance_push()` moves the sequence number once per env step."""
+        step for the exchange; `_begin_step()` moves the sequence number once per env step."""
         self._require_device()
         if world > 8:
             raise ValueError("peer push from the kernels covers one node (at most 8 ranks)")
@@ -306,27 +307,51 @@ class EnvManager(BaseManager):
             B.step_signal = None
             self._push = None
 
-    def _advance_push(self):
-        """new env step: the slot its rows go to, the sequence number that will announce them, and the step (two back) whose
-        arrival from every rank the step waits for before anything is overwritten (agx_push_advance; the position task's
-        one-call step does this inside the library)"""
-        _lib.check(self._lib.agx_push_advance(self._buffers), "agx_push_advance")
-
     # ------------------------------------------------------------------ helpers
-    def _stream(self):
-        """torch's current stream on this device.  Looked up once per public call (step / reset / render ...):
-        torch.cuda.current_stream() costs microseconds and a navigation step makes ~15 launches."""
-        s = self._stream_cache
-        if s is None:
-            s = self._stream_cache = _lib.current_stream(self.device)
-        return s
+    def _stream(self):  # torch's current stream on this device, looked up at every launch (a fraction of a microsecond)
+        return _lib.current_stream(self.device)
 
+    # ---- host state of a step (module docstring) ---------------------------------------------------------------------------
+    REWARD, RESET_SET, OBSERVATION, SENSOR_POSES, TARGETS = "reward", "reset_set", "observation", "sensor_poses", "targets"
     _calls = 0  # public calls so far (reset, reset_idx, step, render ...): a task's single-launch proof is void behind one
 
-    def _new_call(self):
-        self._stream_cache = None
+    @property
+    def _parity(self):
+        return self._buffers.flag_parity if self._buffers is not None else 0
+
+    def mark_produced(self, what):
+        self._produced.add(what)
+
+    def has_produced(self, what):
+        return what in self._produced
+
+    def take_produced(self, what):  # has_produced, and the entry is gone: whoever would have launched `what` skips once
+        had = what in self._produced
+        self._produced.discard(what)
+        return had
+
+    def _begin_call(self, counted=True):
+        """top of every public entry that changes state; `counted=False`: the position task's own one-call step, which must not
+        void its own single-launch proof"""
+        self._produced.clear()
         self._derived_stale = True
-        self._calls += 1
+        if counted:
+            self._calls += 1
+
+    def _begin_step(self, library_advances=False):
+        """a new env step.  `library_advances`: the call that follows flips the parity and moves the peer push itself
+        (agx_position_task_step), and is that task's own step"""
+        self._begin_call(counted=not library_advances)
+        B = self._buffers
+        B.step_counter = self.step_counter & 0x7FFFFFFF  # counter word of the per-step device RNG streams, step_signal
+        if not library_advances:
+            B.flag_parity ^= 1  # the reset flag the previous step's reset kernel cleared
+            if self._push is not None:  # the slot this step's rows go to, the sequence number that will announce them, and the
+                # step (two back) whose arrival from every rank the step waits for before anything is overwritten
+                _lib.check(self._lib.agx_push_advance(self._buffers), "agx_push_advance")
+
+    def _end_step(self):
+        self.step_counter += 1
 
     # ---- lean step (args={"lean_step": True}): AGX_LAUNCH_LEAN for batches far above 65 536 envs, where bytes matter ------
     LEAN_MIN_ENVS = 65537
@@ -469,8 +494,6 @@ class EnvManager(BaseManager):
     # the envs that reset, the world pose of every sensor -- to run in the SAME launch (agx_nav_robot_side: one launch instead
     # of four dependent ones).  Only the per-step reset of task.step() takes it; an explicit reset_idx() stays as it was.
     _nav_side = None
-    _sensor_pose_fresh = False    # the fused launch computed this step's sensor poses: HipSensor.compose_pose skips once
-    _targets_reset_fused = False  # ... and resampled the targets of the reset envs: the task's _reset_targets skips once
 
     def enable_fused_robot_side(self, nav_args):
         self._nav_side = nav_args
@@ -482,14 +505,16 @@ class EnvManager(BaseManager):
         if per_step and self._nav_side is not None and self.post_obs is None and not self.strict_rng:
             _lib.check(self._lib.agx_nav_robot_side(self._params, self._buffers, self.num_envs, self._reset_args,
                                                     _lib.C.byref(self._nav_side), self._stream()), "agx_nav_robot_side")
-            self._sensor_pose_fresh = self._nav_side.num_sensors > 0
-            self._targets_reset_fused = bool(self._nav_side.reset_target)
+            if self._nav_side.num_sensors > 0:  # this step's sensor poses: HipSensor.compose_pose skips once
+                self.mark_produced(self.SENSOR_POSES)
+            if self._nav_side.reset_target:     # the targets of the reset envs: the task's _reset_targets skips once
+                self.mark_produced(self.TARGETS)
             return
         if with_obs and self.post_obs is not None:
             _lib.check(self._lib.agx_post_step_position(self._params, self._buffers, self.num_envs, self._reset_args,
                                                         self.post_obs[0], self.post_obs[1], self._stream()),
                        "agx_post_step_position")
-            self._obs_fresh = True
+            self.mark_produced(self.OBSERVATION)
         else:
             _lib.check(self._lib.agx_reset_masked(self._params, self._buffers, self.num_envs, self._reset_args, self._stream()),
                        "agx_reset_masked")
@@ -498,7 +523,7 @@ class EnvManager(BaseManager):
     @roctx.ranged("EnvManager.reset_idx")
     def reset_idx(self, env_ids=None):
         self._require_device()
-        self._new_call()
+        self._begin_call()
         g = self.global_tensor_dict
         if env_ids is None:
             env_ids = torch.arange(self.num_envs, device=self.device)
@@ -536,13 +561,13 @@ class EnvManager(BaseManager):
 
     def reset_terminated_and_truncated_envs(self):
         g = self.global_tensor_dict
-        if not self._mask_fresh:
+        if not self.has_produced(self.RESET_SET):
             # nobody produced this step's reset set on the device (no fused task epilogue, no agx_reward_* call): derive
             # it from the flags as they stand, like the reference does right here (env_manager.py:364-371) -- stand-alone
             # EnvManager loops (examples/benchmark.py) and user tasks that set `truncations[:]` in torch depend on it
             _lib.check(self._lib.agx_reset_set(self._buffers, self.num_envs, int(self.cfg.env.reset_on_collision), self._stream()),
                        "agx_reset_set")
-            self._mask_fresh = True
+            self.mark_produced(self.RESET_SET)
         if self.strict_rng and int(g["reset_flag"][self._parity].item()) != 0:  # host sync, like the reference's nonzero()/len()
             # the indices themselves (a second synchronisation) only where a draw is shaped by them: per-env controller gains, the
             # obstacles' half-resample, sensor mounts -- the plain position task draws for all N envs whatever the set is
@@ -574,7 +599,6 @@ class EnvManager(BaseManager):
         if not self.strict_rng:  # drawn inside the kernel (Philox keyed by env, step, sub-step)
             self._buffers.disturb = None
             self._buffers.disturb_prob = float(robot.cfg.disturbance.prob_apply_disturbance)
-            self._buffers.step_counter = self.step_counter & 0x7FFFFFFF
             return
         N, rs = self.num_envs, self.random_source
         if self._disturb_buf is None or self._disturb_buf.shape[0] < k:
@@ -606,8 +630,9 @@ class EnvManager(BaseManager):
                                        self._stream()),
                 "agx_env_step",
             )
-        self._reward_fresh = self._mask_fresh = self.task_args is not None
-        self._obs_fresh = False
+        self._produced.difference_update((self.REWARD, self.RESET_SET, self.OBSERVATION))  # (simulate() by hand: of the state before)
+        if self.task_args is not None:  # the fused epilogue wrote the reward, the flags and this step's reset set
+            self._produced.update((self.REWARD, self.RESET_SET))
         self.robot_manager.post_physics_step(num_substeps)
 
     def _simulate_with_external_controller(self, a, k):
@@ -694,8 +719,8 @@ class EnvManager(BaseManager):
             a = a.to(dtype=torch.float32).contiguous()
         if a.shape != (self.num_envs, self.num_robot_actions):
             raise ValueError("Action tensor does not have the correct number of environments")
-        if not self._in_external_simulate:  # BaseMultirotor.step called by hand: a call of its own (stream lookup, derived tensors)
-            self._new_call()
+        if not self._in_external_simulate:  # BaseMultirotor.step called by hand: a call of its own (the record, derived tensors)
+            self._begin_call()
         R = self._robot_plugin_state()
         R.substep = int(self._robot_substep)
         _lib.check(self._lib.agx_robot_step(self._params, self._buffers, self.num_envs, _lib.dptr(a), _lib.C.byref(R), self._stream()),
@@ -742,7 +767,7 @@ class EnvManager(BaseManager):
         """env_actions: [N, num_assets, 6] obstacle twists (world-frame linear + angular velocity), the
         reference's dynamic-environment interface (env_manager.py:399-416, obstacle_manager.py:40-44)."""
         self._require_device()
-        self._new_call()
+        self._begin_step()
         g = self.global_tensor_dict
         k = self.num_physics_steps()
         if env_actions is not None:
@@ -753,17 +778,10 @@ class EnvManager(BaseManager):
             self.env_actions[:] = env_actions
             # the obstacles move first, then the robots fly k sub-steps against their new poses
             self.asset_manager.apply_env_actions(self, self.env_actions, k)
-        # new env step: switch to the reset flag the previous step's reset kernel cleared
-        self._parity ^= 1
-        self._buffers.flag_parity = self._parity
-        # counter word of the per-step device RNG streams (disturbance, observation / LiDAR noise, IMU)
-        self._buffers.step_counter = self.step_counter & 0x7FFFFFFF
-        if self._push is not None:
-            self._advance_push()
         self.simulate(actions, env_actions, k)
         if self._push is not None:
             self._buffers.push_wait_seq = 0  # the env-step kernel has waited for the row slot; the kernels behind it need not
-        self.step_counter += 1
+        self._end_step()
 
     def compute_observations(self):
         """env_manager.py:358-362: collision_tensor |= contact.  The fused step (step / simulate) has already accumulated the flag

@@ -162,8 +162,7 @@ class HipSensor:
 
     def compose_pose(self):
         env = self.g["env_manager"]
-        if env._sensor_pose_fresh:  # this step's poses were written by the fused robot-side launch (agx_nav_robot_side)
-            env._sensor_pose_fresh = False
+        if env.take_produced(env.SENSOR_POSES):  # by the fused robot-side launch (agx_nav_robot_side)
             return
         p = _lib.dptr
         _lib.check(

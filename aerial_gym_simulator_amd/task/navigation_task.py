@@ -226,8 +226,7 @@ class NavigationTask(BaseTask):
             if len(reset_envs) > 0:
                 self.reset_idx(reset_envs.indices)
             return
-        if env._targets_reset_fused:  # done by the launch that reset the robots (agx_nav_robot_side)
-            env._targets_reset_fused = False
+        if env.take_produced(env.TARGETS):  # by the launch that reset the robots (agx_nav_robot_side)
             self.infos = {}
             return
         _lib.check(env._lib.agx_nav_target_reset(env._buffers, env.num_envs, env.num_robot_actions, self._min_ratio, self._max_ratio, None,
@@ -290,7 +289,7 @@ class NavigationTask(BaseTask):
         if (kind is None or env._buffers is None or not actions.is_cuda or actions.dtype is not torch.float32 or not actions.is_contiguous()
                 or actions.shape != (self.num_envs, 4)):
             return self.action_transformation_function(actions)
-        env._new_call()
+        env._begin_call()
         out = torch.empty((self.num_envs, kind[1]), device=actions.device)  # a fresh tensor per step, like the torch form (callers keep references)
         _lib.check(env._lib.agx_action_transform(kind[0], self.num_envs, _lib.dptr(actions), _lib.dptr(out), env._stream()),
                    "agx_action_transform")
@@ -393,12 +392,9 @@ class NavigationTask(BaseTask):
                 ret = self._device_step(transformed_action)
         else:
             graph, ret = entry
-            env._new_call()
-            env._parity ^= 1  # what EnvManager.step does on the host (the kernels' copies are frozen in the graph)
-            env._buffers.flag_parity = env._parity
-            env.step_counter += 1
-            env._reward_fresh = env._obs_fresh = env._mask_fresh = False
+            env._begin_step()  # what EnvManager.step does on the host (the kernels' copies are frozen in the graph)
             graph.replay()
+            env._end_step()
         self._finish_step_host()
         return ret
 
@@ -425,8 +421,7 @@ class NavigationTask(BaseTask):
     def compute_rewards_and_crashes(self, obs_dict):
         env = self.sim_env
         env._require_device()
-        if env._reward_fresh:  # produced by the fused epilogue of agx_env_step
-            env._reward_fresh = False
+        if env.take_produced(env.REWARD):  # by the fused epilogue of agx_env_step
             return self.rewards, self.terminations
         _lib.check(
             env._lib.agx_reward_navigation(env._buffers, env.num_envs, _lib.dptr(self.target_soa), self._rp,
@@ -435,7 +430,7 @@ class NavigationTask(BaseTask):
                                            int(env.cfg.env.reset_on_collision), _lib.dptr(self.rewards), env._stream()),
             "agx_reward_navigation",
         )
-        env._mask_fresh = True  # the reward kernel wrote this step's reset set
+        env.mark_produced(env.RESET_SET)  # the reward kernel wrote this step's reset set
         return self.rewards, self.terminations
 
     def get_return_tuple(self):

@@ -208,17 +208,14 @@ class PositionSetpointTask(BaseTask):
     @roctx.ranged("PositionSetpointTask.step")
     def step(self, actions):
         self.counter += 1
+        self.prev_actions = self.actions  # previous step's tensor (no copy; the reward does not read it)
+        self.actions = actions
+        env = self.sim_env
         if (self._plan is not None and actions.dtype is torch.float32 and actions.is_contiguous() and actions.is_cuda
                 and actions.shape == self._action_shape):  # anything else takes the general path, which raises like the reference
             # fast path: same two launches as the general path below, one host call.  Host time is 0.9 of this step at 8192 envs
             # (bench.py `host.share_of_step`): nothing here allocates or looks anything up twice.
-            self.prev_actions = self.actions  # previous step's tensor (no copy; the reward does not read it)
-            self.actions = actions
-            env = self.sim_env
-            env._stream_cache = None          # (EnvManager._new_call, inlined)
-            env._derived_stale = True
-            B = env._buffers
-            B.step_counter = env.step_counter & 0x7FFFFFFF  # as EnvManager.step (RNG streams, step_signal)
+            env._begin_step(library_advances=True)  # (the library flips the parity and moves the peer push; not a counted call)
             el = self.task_config.episode_len_steps
             if el != self._plan_episode_len:
                 self._plan_task.episode_len = self._plan_episode_len = int(el)
@@ -228,19 +225,12 @@ class PositionSetpointTask(BaseTask):
                 v = (w[0]._version, w[1]._version, w[2]._version, w[3]._version)
                 if v != self._proof_versions or env._calls != self._proof_calls:
                     self._proof_versions, self._proof_calls = v, env._calls
-                    self._plan.proof_min_tag = (B.step_counter + 1) & 0x7FFFFFFF  # only records of this step on count
-            try:
-                rc = self._plan_fn(self._plan_ref, actions.data_ptr(), _lib.current_stream(env.device))
-            finally:
-                env._parity = B.flag_parity  # the library toggles it first: stay in step on the error path too
+                    self._plan.proof_min_tag = (env.step_counter + 1) & 0x7FFFFFFF  # only records of this step on count
+            rc = self._plan_fn(self._plan_ref, actions.data_ptr(), _lib.current_stream(env.device))
             if rc != 0:
                 _lib.check(rc, "agx_position_task_step")
-            env._mask_fresh = env._obs_fresh = False
-            env.step_counter += 1
+            env._end_step()
             return (self.task_obs, self.rewards, self.terminations, self.truncations, self.infos)
-        self.prev_actions = self.actions
-        self.actions = actions
-        env = self.sim_env
         if env.task_args is not None:
             env.task_args.episode_len = int(self.task_config.episode_len_steps)
         env.step(actions=self.actions)
@@ -257,8 +247,7 @@ class PositionSetpointTask(BaseTask):
         """compute_reward + `truncations = sim_steps > episode_len` (reference :205-229,:172-174)."""
         env = self.sim_env
         env._require_device()
-        if env._reward_fresh:  # already produced by the fused epilogue of agx_env_step
-            env._reward_fresh = False
+        if env.take_produced(env.REWARD):  # by the fused epilogue of agx_env_step
             return self.rewards, self.terminations
         _lib.check(
             env._lib.agx_reward_position(env._buffers, env.num_envs, _lib.dptr(self.target_soa),
@@ -266,7 +255,7 @@ class PositionSetpointTask(BaseTask):
                                          _lib.dptr(self.rewards), env._stream()),
             "agx_reward_position",
         )
-        env._mask_fresh = True  # the reward kernel wrote this step's reset set
+        env.mark_produced(env.RESET_SET)  # the reward kernel wrote this step's reset set
         return self.rewards, self.terminations
 
     def get_return_tuple(self):
@@ -279,8 +268,7 @@ class PositionSetpointTask(BaseTask):
         self.task_obs["rewards"] = self.rewards
         self.task_obs["terminations"] = self.terminations
         self.task_obs["truncations"] = self.truncations
-        if env._obs_fresh:  # already written by agx_post_step_position
-            env._obs_fresh = False
+        if env.take_produced(env.OBSERVATION):  # by agx_post_step_position
             return
         _lib.check(
             env._lib.agx_obs_position(env._buffers, env.num_envs, _lib.dptr(self.target_soa),

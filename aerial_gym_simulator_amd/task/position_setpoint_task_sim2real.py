@@ -104,7 +104,7 @@ class PositionSetpointTaskSim2Real(BaseTask):
         _lib.check(
             env._lib.agx_sim2real_pre_step(self.KIND, env._buffers, env.num_envs, _lib.dptr(self.target_soa), _lib.dptr(self.actions),
                                            _lib.dptr(actions), _lib.dptr(self.prev_actions), _lib.dptr(self.prev_dist),
-                                           _lib.dptr(self.prev_actions_vehicle_frame), _lib.current_stream(env.device)),
+                                           _lib.dptr(self.prev_actions_vehicle_frame), env._stream()),
             "agx_sim2real_pre_step",
         )
         self.actions = actions
@@ -156,7 +156,7 @@ class PositionSetpointTaskSim2Real(BaseTask):
                                          _lib.dptr(self.rewards), env._stream()),
             "agx_sim2real_reward",
         )
-        env._mask_fresh = True  # the reward kernel wrote this step's reset set
+        env.mark_produced(env.RESET_SET)  # the reward kernel wrote this step's reset set
         return self.rewards, self.terminations
 
 
