@@ -29,6 +29,7 @@ _FILE_EXPORTS = {
     "task_config.position_setpoint_task_config": {"task_config": "position_setpoint_task_config"},
     "task_config.position_setpoint_task_sim2real_config": {"task_config": "position_setpoint_task_sim2real_config"},
     "task_config.position_setpoint_task_acceleration_sim2real_config": {"task_config": "position_setpoint_task_acceleration_sim2real_config"},
+    "task_config.position_setpoint_task_sim2real_end_to_end_config": {"task_config": "position_setpoint_task_sim2real_end_to_end_config"},
     "task_config.navigation_task_config": {"task_config": "navigation_task_config"},
     "task_config.lidar_navigation_task_config": {"task_config": "lidar_navigation_task_config"},
     "controller_config.lee_controller_config": {"control": "lee_controller_config"},

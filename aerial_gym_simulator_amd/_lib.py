@@ -279,7 +279,19 @@ class AgxLinkFrames(C.Structure):
     _fields_ = [("num_bodies", C.c_int32), ("reserved", C.c_int32), ("rot", (C.c_float * 9) * MAX_BODIES), ("pos", (C.c_float * 3) * MAX_BODIES)]
 
 
-ABI_VERSION = 15  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+class AgxEndToEndLimits(C.Structure):
+    _fields_ = [("min", C.c_float * 4), ("max", C.c_float * 4)]
+
+
+class AgxEndToEndReward(C.Structure):
+    _fields_ = [("z_error_weight", C.c_float), ("pos_gain", C.c_float * 2), ("pos_exp", C.c_float * 2), ("upright_gain", C.c_float),
+                ("upright_exp", C.c_float), ("alignment_gain", C.c_float), ("alignment_exp", C.c_float), ("angvel_gain", C.c_float),
+                ("angvel_exp", C.c_float), ("vel_gain", C.c_float), ("vel_exp", C.c_float), ("hover_thrust", C.c_float),
+                ("action_gain", C.c_float), ("action_exp", C.c_float), ("closer_gain", C.c_float), ("farther_gain", C.c_float),
+                ("diff_gain", C.c_float), ("diff_exp", C.c_float), ("divisor", C.c_float)]
+
+
+ABI_VERSION = 16  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -383,6 +395,13 @@ _SIGNATURES = {
     "agx_sim2real_pre_step": (C.c_int, [C.c_int, C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "agx_sim2real_reward": (C.c_int, [C.c_int, C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "agx_sim2real_obs": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P]),
+    "agx_end_to_end_pre_step": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, C.POINTER(AgxEndToEndLimits), _P, _P, _P]),
+    "agx_end_to_end_reward": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, C.POINTER(AgxEndToEndReward), C.c_float, C.c_int,
+                                        C.c_int, _P, _P]),
+    "agx_end_to_end_obs": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P]),
+    "agx_end_to_end_noise": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P]),
+    "agx_post_step_end_to_end": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, C.POINTER(AgxResetArgs), _P, _P, _P,
+                                           _P, _P, _P, _P]),
     "agx_nav_bookkeeping": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "agx_nav_target_reset": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P,
                                        C.c_int, _P]),

@@ -1,6 +1,6 @@
 """Robot configs: base_quadrotor and base_octarotor
 (aerial_gym/config/robot_config/base_quad_config.py, base_octarotor_config.py) plus the URDF
-constants of resources/robots/{quad,octarotor}/*.urdf as data (``robot_model``)."""
+constants of resources/robots/{quad,octarotor}/*.urdf as data (``robot_model``); magpie, lmf2, tinyprop the same way."""
 import numpy as np
 
 from .sensor_config import (
@@ -362,3 +362,86 @@ class BaseQuadRootLinkControlCfg(BaseQuadCfg):  # base_quad_root_link_control_co
             motor_time_constant_increasing_min, motor_time_constant_increasing_max = 0.01, 0.03
             motor_time_constant_decreasing_min, motor_time_constant_decreasing_max = 0.005, 0.005
             max_thrust, min_thrust = 10, 0
+
+
+_TINYPROP_ARM_RPY = [  # joints base_link_to_arm_motor_0..3 of tinyprop.urdf
+    [-1.5707963267948968, 2.220446049250313e-16, -2.3561944901923453],
+    [1.5707963267948968, 2.220446049250313e-16, -0.7853981633974482],
+    [1.5707963267948968, 0.0, -2.3561944901923453],
+    [-1.5707963267948968, 0.0, -0.7853981633974482],
+]
+_TINYPROP_ARM_XYZ = [[0.08, -0.08, 0.0], [-0.08, -0.08, 0.0], [-0.08, 0.08, 0.0], [0.08, 0.08, 0.0]]
+
+
+class TinyPropCfg:  # tinyprop_config.py:15-166, resources/robots/tinyprop/tinyprop.urdf -- the airframe of the end-to-end task
+    """The robot the reference trains motor-command policies for (position_setpoint_task_sim2real_end_to_end, `no_control`: the
+    action IS the four thrusts, clamped to 0.2 .. 1.2 N by the motor model).  The first airframe here with products of inertia:
+    the base link's tensor is full, the arm links are rotated and the prop links carry full tensors.  Pinned by
+    tests/golden/robot_tinyprop.npz (composite of the reference's URDF)."""
+
+    class init_config:
+        min_init_state = [-0.7, -0.7, -0.7, -_PI / 6, -_PI / 6, -_PI, 1.0, -0.5, -0.5, -0.5, -0.5, -0.5, -0.5]
+        max_init_state = [0.7, 0.7, 0.7, _PI / 6, _PI / 6, _PI, 1.0, 0.5, 0.5, 0.5, 0.5, 0.5, 0.5]
+
+    class sensor_config:
+        enable_camera = False
+        camera_config = BaseDepthCameraConfig
+        enable_lidar = False
+        lidar_config = BaseLidarConfig
+        enable_imu = False
+        imu_config = BaseImuConfig
+
+    class disturbance:
+        enable_disturbance = False
+        prob_apply_disturbance = 0.02
+        max_force_and_torque_disturbance = [0.001, 0.001, 0.001, 0.00004, 0.00004, 0.00004]
+
+    class damping:
+        linvel_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        linvel_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+
+    class robot_asset(_CommonAsset):
+        file = "tinyprop.urdf"
+        name = "tinyprop"
+        angular_damping = 0.01
+        linear_damping = 0.01
+
+    class robot_model:  # tinyprop.urdf: base 0.321 kg, four 13 g props at (+-0.16, +-0.16, 0), four 1 mg arm links half way out
+        base_mass = 0.321
+        base_inertia = [[0.0015914, -0.0000044, 0.0000001], [-0.0000044, 0.0015312, 0.0000031], [0.0000001, 0.0000031, 0.0025329]]
+        # the URDF collision shape is a 0.11 m cube; the collision model here is a sphere of half its width (DESIGN.md "Collision")
+        collision_sphere_radius = 0.055
+        motor_mass = 0.013
+        motor_inertia = [[2e-6, 1e-9, 1e-9], [1e-9, 2e-6, 1e-9], [1e-9, 1e-9, 3e-6]]
+        motor_xyz = [[0.16, -0.16, 0.0], [-0.16, -0.16, 0.0], [-0.16, 0.16, 0.0], [0.16, 0.16, 0.0]]
+        motor_rpy = [[0.0, 0.0, 0.0]] * 4
+        # every joint of this URDF hangs off base_link; `parent` is what composite_body follows
+        links = [dict(name="arm_motor_%d" % j, parent="base_link", mass=0.000001, xyz=_TINYPROP_ARM_XYZ[j], rpy=_TINYPROP_ARM_RPY[j],
+                      inertia=[[1e-9] * 3] * 3) for j in range(4)]
+
+    class control_allocator_config:
+        num_motors = 4
+        force_application_level = "motor_link"
+        application_mask = [5, 6, 7, 8]
+        motor_directions = [1, -1, 1, -1]
+        allocation_matrix = [
+            [0.0, 0.0, 0.0, 0.0],
+            [0.0, 0.0, 0.0, 0.0],
+            [1.0, 1.0, 1.0, 1.0],
+            [-0.16, -0.16, 0.16, 0.16],
+            [-0.16, 0.16, 0.16, -0.16],
+            [-0.01, 0.01, -0.01, 0.01],
+        ]
+
+        class motor_model_config:
+            use_rps = True
+            motor_thrust_constant_min = motor_thrust_constant_max = 0.00001286412
+            motor_time_constant_increasing_min = motor_time_constant_increasing_max = 0.047
+            motor_time_constant_decreasing_min = motor_time_constant_decreasing_max = 0.047
+            max_thrust, min_thrust = 1.2, 0.2
+            max_thrust_rate = 100000.0
+            thrust_to_torque_ratio = 0.01
+            use_discrete_approximation = True
+            integration_scheme = "rk4"

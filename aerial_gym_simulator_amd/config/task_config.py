@@ -49,6 +49,39 @@ class position_setpoint_task_acceleration_sim2real_config(position_setpoint_task
     reward_parameters = {}
 
 
+def end_to_end_process_actions(actions, min_limit, max_limit):
+    """position_setpoint_task_sim2real_end_to_end_config.py:28-33: policy output in [-1, 1] -> motor thrust command"""
+    actions_clipped = torch.clamp(actions, -1, 1)
+    return actions_clipped * (max_limit - min_limit) / 2 + (max_limit + min_limit) / 2
+
+
+class position_setpoint_task_sim2real_end_to_end_config:  # position_setpoint_task_sim2real_end_to_end_config.py:6-33 (EVAL == False)
+    seed = 56
+    sim_name = "base_sim"
+    env_name = "empty_env"
+    robot_name = "tinyprop"
+    controller_name = "no_control"
+    args = {}
+    num_envs = 4096
+    use_warp = False
+    headless = True
+    device = "cuda:0"
+    privileged_observation_space_dim = 0
+    action_space_dim = 4
+    observation_space_dim = 15
+    episode_len_steps = 600
+    return_state_before_reset = False
+    reward_parameters = {}
+    crash_dist = 1.5
+    # (the reference makes these on cuda:0 at import; here on the CPU, so that the module imports without a GPU -- the task moves
+    # them to its device)
+    action_limit_max = torch.ones(action_space_dim) * 1.2
+    action_limit_min = torch.ones(action_space_dim) * 0.2
+    # the stock rescale has a one-launch device form (agx_end_to_end_pre_step); the task uses it while the config still carries
+    # THE function object above, and calls whatever a user puts here instead as the torch code it is
+    process_actions_for_task = staticmethod(end_to_end_process_actions)
+
+
 class navigation_task_config:
     seed = -1
     sim_name = "base_sim"

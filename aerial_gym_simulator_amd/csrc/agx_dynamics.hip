@@ -138,6 +138,7 @@ static bool quad_loop_kernel_usable(const AgxRobotParams *P, const AgxEnvBuffers
 #include "agx_dyn_quad.h"
 #include "agx_dyn_robot.h"
 #include "agx_dyn_reset.h"
+#include "agx_dyn_end_to_end.h"
 #include "agx_dyn_position_step.h"
 
 // Which env-step kernel a launch runs, decided ONCE: agx_env_step switches on it and agx_env_step_kernel prints it (bench.py and the

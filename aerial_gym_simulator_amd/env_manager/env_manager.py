@@ -2,7 +2,7 @@
 HIP library instead of Isaac Gym + Warp + torch op chains.
 
 Which launches make one `task.step()` is DESIGN.md section 1 (position task: one or two, in one host call; navigation: six;
-sim2real: six).  All are stream-ordered on torch's current stream, looked up at every launch, with no host synchronisation
+sim2real: six; end-to-end: four).  All are stream-ordered on torch's current stream, looked up at every launch, with no host synchronisation
 unless the caller asks for the reset set as indices or `strict_rng` is requested.
 
 The EnvManager owns the host state of a step, and nobody else assigns it:
@@ -86,6 +86,8 @@ class EnvManager(BaseManager):
         self._produced = set()  # the record: what this step's launches have already produced
         self.task_args = None   # AgxTaskArgs: reward / flags fused into the env-step launch
         self.post_obs = None    # (target_ptr, obs_ptr): observation fused into the reset launch
+        self.post_step_launch = None  # callable: a task's own reset + observation launch, in place of the per-step reset launch
+        self.reset_draw_sets = 1      # strict_rng: sets of reset draws a resetting step consumes (a task whose reference resets twice: 2)
         self.global_tensor_dict = TensorDict()
         self.keep_in_env = None
         self.step_counter = 0
@@ -510,7 +512,10 @@ class EnvManager(BaseManager):
             if self._nav_side.reset_target:     # the targets of the reset envs: the task's _reset_targets skips once
                 self.mark_produced(self.TARGETS)
             return
-        if with_obs and self.post_obs is not None:
+        if with_obs and per_step and self.post_step_launch is not None:
+            self.post_step_launch()
+            self.mark_produced(self.OBSERVATION)
+        elif with_obs and self.post_obs is not None:
             _lib.check(self._lib.agx_post_step_position(self._params, self._buffers, self.num_envs, self._reset_args,
                                                         self.post_obs[0], self.post_obs[1], self._stream()),
                        "agx_post_step_position")
@@ -575,7 +580,8 @@ class EnvManager(BaseManager):
             needs_ids = (self._randomize_gains or (self.scene.num_assets > 0 and int(g["num_obstacles_in_env"]) > 0)
                          or (sensor is not None and sensor.cfg.randomize_placement))
             env_ids = g["reset_mask"].nonzero(as_tuple=False).squeeze(-1) if needs_ids else None
-            self._draw_reset_randoms(env_ids)
+            for _ in range(self.reset_draw_sets):  # (every set fills the same tensors: the reset launch sees the last one)
+                self._draw_reset_randoms(env_ids)
         self._launch_reset(with_obs=True, per_step=True)
         return ResetSet(g["reset_mask"])
 

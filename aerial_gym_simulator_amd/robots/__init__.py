@@ -14,6 +14,7 @@ from ..config.robot_config import (
     LMF2Cfg,
     LMF2With64x48CameraCfg,
     MagpieCfg,
+    TinyPropCfg,
 )
 from ..registry.robot_registry import robot_registry
 from .base_multirotor import BaseMultirotor
@@ -32,3 +33,4 @@ robot_registry.register("base_quadrotor_with_camera_imu", BaseMultirotor, BaseQu
 robot_registry.register("lmf2", BaseMultirotor, LMF2Cfg)
 robot_registry.register("lmf2_with_camera_64x48", BaseMultirotor, LMF2With64x48CameraCfg)
 robot_registry.register("base_quad_root_link_control", BaseMultirotor, BaseQuadRootLinkControlCfg)
+robot_registry.register("tinyprop", BaseMultirotor, TinyPropCfg)  # robots/__init__.py of the reference: the end-to-end task's airframe

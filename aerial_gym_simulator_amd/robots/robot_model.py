@@ -28,17 +28,46 @@ def rpy_to_matrix(roll, pitch, yaw):
     )
 
 
+def link_poses(model):
+    """[(mass, t[3], R[3,3], I[3,3])] of the entries of ``model.links`` in the base-link frame -- the links next to the base link
+    and the motors (tinyprop's arm links): {name, parent, mass, xyz, rpy, inertia}, the pose being that of the URDF joint, i.e.
+    relative to the PARENT link ("base_link" or an earlier entry), composed here along the chain."""
+    frames = {"base_link": (np.zeros(3), np.eye(3))}
+    out = []
+    for link in getattr(model, "links", None) or []:
+        pt, pR = frames[link.get("parent", "base_link")]
+        R = pR @ rpy_to_matrix(*link.get("rpy", [0.0, 0.0, 0.0]))
+        t = pt + pR @ np.asarray(link["xyz"], dtype=np.float64)
+        frames[link["name"]] = (t, R)
+        out.append((float(link["mass"]), t, R, np.asarray(link["inertia"], dtype=np.float64)))
+    return out
+
+
 def composite_body(model):
-    """(mass, com[3], inertia[3,3]) of base link + point-mass motors, float64."""
+    """(mass, com[3], inertia[3,3]) of base link + motors + the further links of ``model.links``, float64: each link's own tensor
+    rotated into the base frame (R I R^T) plus the parallel-axis term.  ``motor_inertia``: a scalar k (k * identity: rotated
+    frames do not matter) or a full 3 x 3 tensor in the motor link's frame (``motor_rpy``)."""
     xyz = np.asarray(model.motor_xyz, dtype=np.float64)
     m_motor = float(model.motor_mass)
+    links = link_poses(model)
     mass = float(model.base_mass) + m_motor * len(xyz)
-    com = (m_motor * xyz.sum(axis=0)) / mass
+    first_moment = m_motor * xyz.sum(axis=0)
+    for m, t, _, _ in links:
+        mass += m
+        first_moment = first_moment + m * t
+    com = first_moment / mass
     inertia = np.asarray(model.base_inertia, dtype=np.float64).copy()
-    # the motor links' own (diagonal) inertia, when the URDF gives one: rotated frames do not matter for k * I
-    inertia += len(xyz) * float(getattr(model, "motor_inertia", 0.0)) * np.eye(3)
-    # base link sits at the origin; shift it and every motor to the common COM
-    for m, r in [(float(model.base_mass), np.zeros(3))] + [(m_motor, p) for p in xyz]:
+    motor_inertia = getattr(model, "motor_inertia", 0.0)
+    if np.ndim(motor_inertia) == 0:
+        inertia += len(xyz) * float(motor_inertia) * np.eye(3)
+    else:
+        for rpy in model.motor_rpy:
+            R = rpy_to_matrix(*rpy)
+            inertia += R @ np.asarray(motor_inertia, dtype=np.float64) @ R.T
+    for _, _, R, I in links:
+        inertia += R @ I @ R.T
+    # base link sits at the origin; shift it, every motor and every further link to the common COM
+    for m, r in [(float(model.base_mass), np.zeros(3))] + [(m_motor, p) for p in xyz] + [(m, t) for m, t, _, _ in links]:
         d = r - com
         inertia += m * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
     return mass, com, inertia

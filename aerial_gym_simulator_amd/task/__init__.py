@@ -5,12 +5,14 @@ from ..config.task_config import (
     navigation_task_config,
     position_setpoint_task_acceleration_sim2real_config,
     position_setpoint_task_config,
+    position_setpoint_task_sim2real_end_to_end_config,
     position_setpoint_task_sim2real_config,
 )
 from ..registry.task_registry import task_registry
 from .lidar_navigation_task import LiDARNavigationTask
 from .navigation_task import NavigationTask
 from .position_setpoint_task import PositionSetpointTask
+from .position_setpoint_task_sim2real_end_to_end import PositionSetpointTaskSim2RealEndToEnd
 from .position_setpoint_task_sim2real import PositionSetpointTaskAccelerationSim2Real, PositionSetpointTaskSim2Real
 
 task_registry.register_task("position_setpoint_task", PositionSetpointTask, position_setpoint_task_config)
@@ -22,3 +24,6 @@ task_registry.register_task("navigation_task_fully_actuated_lidar", NavigationTa
 task_registry.register_task("position_setpoint_task_sim2real", PositionSetpointTaskSim2Real, position_setpoint_task_sim2real_config)
 task_registry.register_task("position_setpoint_task_acceleration_sim2real", PositionSetpointTaskAccelerationSim2Real,
                             position_setpoint_task_acceleration_sim2real_config)
+# ... and the one whose policy commands the motor thrusts of the tinyprop directly
+task_registry.register_task("position_setpoint_task_sim2real_end_to_end", PositionSetpointTaskSim2RealEndToEnd,
+                            position_setpoint_task_sim2real_end_to_end_config)

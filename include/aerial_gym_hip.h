@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 15
+#define AGX_ABI_VERSION 16
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -452,6 +452,54 @@ int agx_sim2real_reward(int kind, const AgxEnvBuffers *buf, int num_envs, const 
 int agx_sim2real_obs(const AgxEnvBuffers *buf, int num_envs, const float *target, const float *noise, float *obs,
                      void *stream);
 
+/* ---- the end-to-end motor-command set-point task (position_setpoint_task_sim2real_end_to_end.py: tinyprop, no_control) ----
+ * Four launches per step: pre-step, the env step, reward, and the step's tail (reset + observation + bookkeeping).  target,
+ * prev_position and prev_pos_error are [3][N]; actions / prev_actions are the task's own [N][4] row-major tensors, 16-byte
+ * aligned; obs is [N][15] row-major.
+ *
+ * Pre-step: step() up to sim_env.step (:164-168).  actions <- clamp(actions_in, -1, 1) * (max - min) / 2 + (max + min) / 2 per
+ * column (task_config.process_actions_for_task, ..._end_to_end_config.py:28-33; actions_in is neither kept nor changed), and
+ * prev_position <- robot_position.  limits: HOST pointer, passed to the kernel by value.                                     */
+typedef struct AgxEndToEndLimits {
+  float min[4], max[4];  /* task_config.action_limit_min / action_limit_max */
+} AgxEndToEndLimits;
+int agx_end_to_end_pre_step(const AgxEnvBuffers *buf, int num_envs, const float *actions_in, const AgxEndToEndLimits *limits,
+                            float *actions, float *prev_position, void *stream);
+
+/* The constants of compute_reward (:267-309) as one table (HOST pointer, passed by value): a sibling task with other numbers is
+ * another instance.  exp_func(x, gain, exp) = gain * exp(-exp * x * x), exp_penalty_func = gain * (exp(-exp * x * x) - 1).   */
+typedef struct AgxEndToEndReward {
+  float z_error_weight;               /* pos_error[:, 2] *= 11 (:282), after both distances were taken                  */
+  float pos_gain[2], pos_exp[2];      /* the two per-component position terms (:283): (10, 10) and (2, 2)               */
+  float upright_gain, upright_exp;    /* on 1 - quat_axis(q, 2).z (:285-287): 2.5, 5                                    */
+  float alignment_gain, alignment_exp;/* on 1 - quat_axis(q, 0).x (:289-291): 6, 5                                      */
+  float angvel_gain, angvel_exp;      /* per component of robot_body_angvel (:293): 0.3, 10                             */
+  float vel_gain, vel_exp;            /* per component of robot_linvel (:294): 1, 5                                     */
+  float hover_thrust;                 /* 9.81 * 0.372 / 4 (:296): a double, rounded to float once                       */
+  float action_gain, action_exp;      /* penalty on action - hover_thrust (:297): 0.01, 10                              */
+  float closer_gain, farther_gain;    /* the two-sided towards_goal_reward (:300): 10, 15                               */
+  float diff_gain, diff_exp;          /* penalty on action - prev_action (:303): 1.3, 6                                 */
+  float divisor;                      /* :305: 100                                                                      */
+} AgxEndToEndReward;
+/* Reward: compute_rewards_and_crashes + compute_reward (:232-252, 267-309) and `truncations = sim_steps > episode_len` (:176-178).
+ * Reads buf->state (position, orientation, world linear velocity) and robot_body_angvel of buf->derived as the env step left
+ * them; writes reward[N], ORs `|target - position| > crash_dist` into crashes (the reward is NOT replaced there) and leaves
+ * reset_mask / reset_flag[flag_parity] exactly as agx_sim2real_reward does (env_manager.py:364-371).                           */
+int agx_end_to_end_reward(const AgxEnvBuffers *buf, int num_envs, const float *target, const float *actions,
+                          const float *prev_actions, const float *prev_pos_error, const AgxEndToEndReward *constants,
+                          float crash_dist, int episode_len, int reset_on_collision, float *reward, void *stream);
+
+/* Observation: process_obs_for_task (:204-225).  obs row = position error + 0.001 z_p | rotation_6d of the attitude whose "ZYX"
+ * Euler angles carry pi / 1032 z_o each (pytorch3d quaternion_to_matrix -> matrix_to_euler_angles -> euler_angles_to_matrix ->
+ * matrix_to_rotation_6d; no clamp in front of asin: NaN where the reference gives NaN) | robot_linvel + 0.002 z_v |
+ * robot_body_angvel + 0.001 z_w.  noise: standard normals [4][N][3] in the reference's draw order (position, orientation, linear
+ * velocity, angular velocity), or NULL = twelve normals per env from the device generator, a function of (rng_seed, env_index_base
+ * + env, env step).  Exchange rows (buf->step_rows) are not written for this observation: the call refuses them.               */
+int agx_end_to_end_obs(const AgxEnvBuffers *buf, int num_envs, const float *target, const float *noise, float *obs,
+                       void *stream);
+/* Diagnostic: noise_out [4][N][3] <- the normals the NULL-noise form above draws at this env step.                            */
+int agx_end_to_end_noise(const AgxEnvBuffers *buf, int num_envs, float *noise_out, void *stream);
+
 /* The reset set of EnvManager.reset_terminated_and_truncated_envs (env_manager.py:364-371) from the flags as they are:
  * reset_mask = crashes * reset_on_collision | truncations, reset_flag[flag_parity] |= any.  For callers that did not
  * run one of the task reward kernels above this step (stand-alone EnvManager; tasks that set truncations in torch). */
@@ -555,6 +603,14 @@ int agx_nav_robot_side(const AgxRobotParams *params, const AgxEnvBuffers *buf, i
  * render between reset and observation).                                                  */
 int agx_post_step_position(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs,
                            const AgxResetArgs *args, const float *target, float *obs, void *stream);
+
+/* The tail of step() of the end-to-end task (position_setpoint_task_sim2real_end_to_end.py:180-190, return_state_before_reset
+ * False) in one launch: the masked reset as the call of that name performs it; the task's own reset_idx (:146-153) -- when some env
+ * resets, the target of EVERY env goes back to zero; the end-to-end observation (see there for `noise`) on the post-reset tensors;
+ * then prev_actions <- actions (:189) and prev_pos_error <- target - robot_position (:190).                                     */
+int agx_post_step_end_to_end(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs, const AgxResetArgs *args,
+                             float *target, const float *noise, float *obs, const float *actions, float *prev_actions,
+                             float *prev_pos_error, void *stream);
 
 /* One task.step() of the position-setpoint task as a single host call.  Toggles buf->flag_parity first, exactly like the
  * host does once per env step.
