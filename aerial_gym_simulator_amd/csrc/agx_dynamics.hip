@@ -159,12 +159,24 @@ static EnvStepChoice choose_env_step(const AgxRobotParams *P, const AgxEnvBuffer
   return EnvStepChoice{ENV_STEP_ONE_LANE, P->num_motors, P->controller, k == 1, block == 64, block, blocks_for(n, block)};
 }
 
+// Dynamic LDS one launch may ask for without saying so first, and the most the 256-thread instance can ask for (obstacles, k = 32).
+constexpr size_t kLdsDefaultMax = 64 * 1024;
+constexpr size_t kEnvStepLdsMax = (size_t)AGX_MAX_SUBSTEPS * 3 * 256 * sizeof(float);
+static_assert(kEnvStepLdsMax <= 160 * 1024, "the sub-step positions of a 256-thread workgroup must fit the CU's 160 KiB of LDS");
+
 template <int M, int CTRL>
-static void launch_env_step(const EnvStepChoice &c, size_t lds, hipStream_t stream, const AgxRobotParams &P, const AgxEnvBuffers &B, int n,
-                            const float *actions_in, int k, const AgxTaskArgs &T) {
+static int launch_env_step(const EnvStepChoice &c, size_t lds, hipStream_t stream, const AgxRobotParams &P, const AgxEnvBuffers &B, int n,
+                           const float *actions_in, int k, const AgxTaskArgs &T) {
   const auto kernel = c.single ? (c.wide ? k_env_step<M, CTRL, true, true> : k_env_step<M, CTRL, true, false>)
                                : (c.wide ? k_env_step<M, CTRL, false, true> : k_env_step<M, CTRL, false, false>);
+  if (lds > kLdsDefaultMax) {
+    // 256-thread workgroups with obstacles and k >= 22 sub-steps: opted in as the LBVH build is (agx_scene.hip).  Off the hot
+    // path: every other launch stays below the default and does not come here.
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEnvStepLdsMax);
+    AGX_REQUIRE(e == hipSuccess, "hipFuncSetAttribute(k_env_step, %zu bytes of LDS): %s", lds, hipGetErrorString(e));
+  }
   hipLaunchKernelGGL(kernel, dim3(c.grid), dim3(c.block), lds, stream, P, B, n, actions_in, k, T);
+  return AGX_OK;
 }
 
 extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
@@ -221,7 +233,8 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
 #undef AGX_QUAD_LOOP
     return check_launch("agx_env_step");
   }
-  AGX_DISPATCH_M(c.M, AGX_DISPATCH_CTRL(c.ctrl, launch_env_step<kM, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)));
+  AGX_REQUIRE(lds <= kEnvStepLdsMax, "agx_env_step needs %zu bytes of LDS (> %zu)", lds, kEnvStepLdsMax);
+  AGX_DISPATCH_M(c.M, AGX_DISPATCH_CTRL(c.ctrl, if (int e = launch_env_step<kM, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)) return e));
   return check_launch("agx_env_step");
 }
 
