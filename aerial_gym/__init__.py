@@ -32,6 +32,7 @@ _FILE_EXPORTS = {
     "task_config.position_setpoint_task_sim2real_end_to_end_config": {"task_config": "position_setpoint_task_sim2real_end_to_end_config"},
     "task_config.navigation_task_config": {"task_config": "navigation_task_config"},
     "task_config.lidar_navigation_task_config": {"task_config": "lidar_navigation_task_config"},
+    "task_config.radar_navigation_task_config": {"task_config": "radar_navigation_task_config"},
     "controller_config.lee_controller_config": {"control": "lee_controller_config"},
     "controller_config.lee_controller_config_octarotor": {"control": "lee_controller_config_octarotor"},
     "controller_config.magpie_controller_config": {"control": "magpie_controller_config"},

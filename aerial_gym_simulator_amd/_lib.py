@@ -291,7 +291,7 @@ class AgxEndToEndReward(C.Structure):
                 ("diff_gain", C.c_float), ("diff_exp", C.c_float), ("divisor", C.c_float)]
 
 
-ABI_VERSION = 16  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 17  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -414,6 +414,14 @@ _SIGNATURES = {
         [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P],
     ),
     "agx_reward_lidar_navigation": (
+        C.c_int,
+        [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.c_float, _P, _P, C.c_int, C.c_int, _P, _P],
+    ),
+    "agx_radar_image_obs": (
+        C.c_int,
+        [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P],
+    ),
+    "agx_reward_radar_navigation": (
         C.c_int,
         [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.c_float, _P, _P, C.c_int, C.c_int, _P, _P],
     ),

@@ -12,6 +12,7 @@ from .sensor_config import (
     Lidar32x512Config,
     RSLidar_Airy_Config,
     StereoCameraConfig,
+    fake_radar_config,
 )
 
 _PI = float(np.pi)
@@ -341,6 +342,15 @@ class LMF2With64x48CameraCfg(LMF2Cfg):
 
     class sensor_config(LMF2Cfg.sensor_config):
         camera_config = DepthCamera64x48Config
+
+
+class LMF2RadarCfg(LMF2Cfg):  # lmf2_radar_config.py:18-180: lmf2_config.py with the camera off and the fake radar on, nothing else
+    """The robot of the reference's `radar_navigation_task` (radar_navigation_task_config.py:9-11)."""
+
+    class sensor_config(LMF2Cfg.sensor_config):
+        enable_camera = False
+        enable_lidar = True
+        lidar_config = fake_radar_config
 
 
 class BaseQuadRootLinkControlCfg(BaseQuadCfg):  # base_quad_root_link_control_config.py:18-53

@@ -111,6 +111,30 @@ class RSLidar_Airy_Config(BaseLidarConfig):  # rslidar_airy_config.py:4-35 (dome
         pixel_dropout_prob = 0.0
 
 
+class fake_radar_config(BaseLidarConfig):  # fake_radar_config.py:4-70 (the forward-looking radar of the radar-navigation task)
+    height, width = 48, 120
+    horizontal_fov_deg_min, horizontal_fov_deg_max = -60, 60
+    vertical_fov_deg_min, vertical_fov_deg_max = -60, 60
+    max_range, min_range = 10.0, 0.2
+    return_pointcloud = True
+    pointcloud_in_world_frame = True
+    segmentation_camera = False
+    euler_frame_rot_deg = [0.0, 0.0, 0.0]
+    normalize_range = False
+    far_out_of_range_value, near_out_of_range_value = _oor(max_range, normalize_range)
+    randomize_placement = True
+    min_translation, max_translation = [0.07, -0.06, 0.02], [0.12, 0.03, 0.06]
+    min_euler_rotation_deg, max_euler_rotation_deg = [-5.0, -5.0, -5.0], [5.0, 5.0, 5.0]
+    nominal_position = [0.10, 0.0, 0.03]
+    nominal_orientation_euler_deg = [0.0, 0.0, 0.0]
+
+    class sensor_noise:
+        enable_sensor_noise = False
+        std_a, std_b, std_c = 3.08287454e-06, -4.07347360e-06, 5.30757302e-03
+        mean_offset = -0.025
+        pixel_dropout_prob = 0.01
+
+
 class BaseNormalFaceIDLidarConfig(BaseLidarConfig):
     """sensor_type the reference's WarpSensor accepts (warp_sensor.py:63-70) without shipping a config."""
 

@@ -263,6 +263,43 @@ class lidar_navigation_task_config:  # lidar_navigation_task_config.py:5-108
         return out
 
 
+class radar_navigation_task_config(lidar_navigation_task_config):  # radar_navigation_task_config.py:5-109
+    """The LiDAR-navigation recipe on `lmf2_radar` (lmf2 + a 48 x 120 radar of +-60 degrees) in env_with_obstacles.  The reference's
+    file repeats lidar_navigation_task_config.py and changes the three names and `headless`; the 22 reward parameters, the curriculum
+    (25 .. 70) and the action transformation (2 a[0:3], a[3] pi / 3: the inherited function, with its one-launch device form) are
+    the same values.  The radar task has no low-row noise (radar_navigation_task.py:6-21): no `lidar_low_noise_row0`."""
+
+    seed = -1
+    sim_name = "base_sim"
+    env_name = "env_with_obstacles"
+    robot_name = "lmf2_radar"
+    controller_name = "lmf2_acceleration_control"
+    args = {}
+    num_envs = 512
+    use_warp = True
+    headless = False
+    device = "cuda:0"
+    observation_space_dim = 13 + 4 + 16 * 20  # root state + actions + 3 x 6 min-pooled 48 x 120 radar image
+    privileged_observation_space_dim = 0
+    action_space_dim = 4
+    episode_len_steps = 110
+    return_state_before_reset = False
+    target_min_ratio = [0.90, 0.15, 0.15]
+    target_max_ratio = [0.92, 0.80, 0.80]
+    lidar_pool = (3, 6)  # max_pool2d kernel of process_image_observation (:54-55)
+    lidar_low_noise_row0 = None
+
+    reward_parameters = dict(lidar_navigation_task_config.reward_parameters)  # radar_navigation_task_config.py:30-53: the same table
+    REWARD_PARAMETER_ORDER = lidar_navigation_task_config.REWARD_PARAMETER_ORDER
+
+    class vae_config:
+        use_vae = False
+
+    class curriculum(lidar_navigation_task_config.curriculum):
+        min_level = 25
+        max_level = 70
+
+
 # the built-in transformations have a one-launch device form (agx_action_transform); a task uses it when the config still
 # carries THE function object below (anything a user puts there instead runs as the torch code it is)
 navigation_task_config.action_transformation_function.agx_kind = (1, 4)

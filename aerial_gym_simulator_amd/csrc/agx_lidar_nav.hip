@@ -6,6 +6,14 @@
 //   k_reward_lidar_navigation   compute_rewards_and_crashes + compute_reward (:472-719) + truncation (:399-403)
 //   k_obs_lidar_navigation      process_obs_for_task (:440-470)
 //
+// and the two places where the radar navigation task (aerial_gym/task/radar_navigation_task/radar_navigation_task.py, a subclass
+// of the LiDAR task on `lmf2_radar` + a 48 x 120 fake radar of +-60 degrees) differs from it:
+//
+//   k_radar_image_obs           process_image_observation (:24-63) + add_noise_to_downsampled_lidar_data (:6-21): the same ranges,
+//                               time to collision and min-pool; 3 % of the cells += U(0.2, 10), then 80 % of the cells = -1
+//   k_reward_lidar_navigation<true>   compute_reward (:179-342): negative_x_vel_penalty clamps the x velocity with max = 0 (:242-246)
+//                               where the LiDAR task's (:616-620) clamps it with min = 0
+//
 // All three are epilogue work on data the env-step and ray-cast kernels left in HBM: one pass each,
 // HBM bound (the image kernel reads the 69 KB point cloud of an env exactly once).
 #include "agx_common.h"
@@ -22,20 +30,14 @@ struct LidarNavParams {
   float rp[22];
 };
 
-// One workgroup per env.  Ranges of the H x W rays go to LDS (clipped), the time to collision is a
+// The image kernels: one workgroup per env.  Ranges of the H x W rays go to LDS (clipped), the time to collision is a
 // workgroup min-reduction, the ph x pw min-pool reads LDS.
-__global__ void __launch_bounds__(256) k_lidar_image_obs(AgxEnvBuffers B, int n, int H, int W, int ph, int pw, int low_row0,
-                                                          const float *__restrict__ pointcloud,
-                                                          const float *__restrict__ noise_mask,
-                                                          const float *__restrict__ noise_val,
-                                                          const float *__restrict__ max_mask,
-                                                          const float *__restrict__ low_mask,
-                                                          const float *__restrict__ low_val, int device_noise, int vec4,
-                                                          float *__restrict__ ttc_out, float *__restrict__ ds_out) {
-  extern __shared__ float lds[];  // [H * W] clipped ranges + [4] wave minima
-  const int i = blockIdx.x, tid = threadIdx.x;
-  const int npts = H * W;
-  float *rng = lds, *wmin = lds + npts;
+//
+// The point pass of env i, shared by both kernels: every point's clipped range to rng[] (LDS), the thread's minimum time to
+// collision returned.
+AGX_DEV float image_point_pass(const AgxEnvBuffers &B, int n, int i, int npts, const float *__restrict__ pointcloud, int vec4,
+                               float *rng) {
+  const int tid = threadIdx.x;
   const V3 p = V3{B.state[0 * n + i], B.state[1 * n + i], B.state[2 * n + i]};
   const V3 lv = V3{B.state[7 * n + i], B.state[8 * n + i], B.state[9 * n + i]};
   const float *pc = pointcloud + (size_t)i * npts * 3;
@@ -90,6 +92,12 @@ __global__ void __launch_bounds__(256) k_lidar_image_obs(AgxEnvBuffers B, int n,
       for (int q = 0; q < 4; ++q) point(min(j0 + q * (int)blockDim.x, npts - 1), raw[q][0], raw[q][1], raw[q][2]);
     }
   }
+  return tmin;
+}
+// the workgroup's minimum of the threads' times to collision, clamped to [0, 10] -> ttc_out[i]; ends in the barrier after which
+// every range of the env is in LDS
+AGX_DEV void image_time_to_collision(float tmin, float *wmin, int i, float *__restrict__ ttc_out) {
+  const int tid = threadIdx.x;
   for (int off = 32; off > 0; off >>= 1) tmin = fminf(tmin, __shfl_xor(tmin, off));
   if ((tid & 63) == 0) wmin[tid >> 6] = tmin;
   __syncthreads();
@@ -98,12 +106,33 @@ __global__ void __launch_bounds__(256) k_lidar_image_obs(AgxEnvBuffers B, int n,
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fminf(t, wmin[w]);
     ttc_out[i] = t < 0.0f ? 0.0f : (t > 10.0f ? 10.0f : t);
   }
+}
+// minimum of the ph x pw block (cy, cx) of the clipped ranges
+AGX_DEV float image_pool_min(const float *rng, int W, int ph, int pw, int cy, int cx) {
+  float m = INFINITY;
+  for (int y = cy * ph; y < (cy + 1) * ph; ++y)
+    for (int x = cx * pw; x < (cx + 1) * pw; ++x) m = fminf(m, rng[y * W + x]);
+  return m;
+}
+
+__global__ void __launch_bounds__(256) k_lidar_image_obs(AgxEnvBuffers B, int n, int H, int W, int ph, int pw, int low_row0,
+                                                          const float *__restrict__ pointcloud,
+                                                          const float *__restrict__ noise_mask,
+                                                          const float *__restrict__ noise_val,
+                                                          const float *__restrict__ max_mask,
+                                                          const float *__restrict__ low_mask,
+                                                          const float *__restrict__ low_val, int device_noise, int vec4,
+                                                          float *__restrict__ ttc_out, float *__restrict__ ds_out) {
+  extern __shared__ float lds[];  // [H * W] clipped ranges + [4] wave minima
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int npts = H * W;
+  float *rng = lds, *wmin = lds + npts;
+  const float tmin = image_point_pass(B, n, i, npts, pointcloud, vec4, rng);
+  image_time_to_collision(tmin, wmin, i, ttc_out);
   const int oh = H / ph, ow = W / pw, cells = oh * ow;
   for (int c = tid; c < cells; c += blockDim.x) {
     const int cy = c / ow, cx = c % ow;
-    float m = INFINITY;
-    for (int y = cy * ph; y < (cy + 1) * ph; ++y)
-      for (int x = cx * pw; x < (cx + 1) * pw; ++x) m = fminf(m, rng[y * W + x]);
+    float m = image_pool_min(rng, W, ph, pw, cy, cx);
     const size_t g = (size_t)i * cells + c;
     if (device_noise) {
       // u0 < 0.03: += U(0.2, 10); u2 < 0.02: = 10; rows >= low_row0 and u3 < 0.02: = U(0.2, 1)
@@ -121,6 +150,38 @@ __global__ void __launch_bounds__(256) k_lidar_image_obs(AgxEnvBuffers B, int n,
   }
 }
 
+// radar_navigation_task.py:6-21 after the same point pass: no max-range mask, no low-row mask; an invalid cell reads 1 / -1 = -1
+__global__ void __launch_bounds__(256) k_radar_image_obs(AgxEnvBuffers B, int n, int H, int W, int ph, int pw,
+                                                          const float *__restrict__ pointcloud,
+                                                          const float *__restrict__ noise_mask,
+                                                          const float *__restrict__ noise_val,
+                                                          const float *__restrict__ invalid_mask, int device_noise, int vec4,
+                                                          float *__restrict__ ttc_out, float *__restrict__ ds_out) {
+  extern __shared__ float lds[];  // [H * W] clipped ranges + [4] wave minima
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int npts = H * W;
+  float *rng = lds, *wmin = lds + npts;
+  const float tmin = image_point_pass(B, n, i, npts, pointcloud, vec4, rng);
+  image_time_to_collision(tmin, wmin, i, ttc_out);
+  const int oh = H / ph, ow = W / pw, cells = oh * ow;
+  for (int c = tid; c < cells; c += blockDim.x) {
+    float m = image_pool_min(rng, W, ph, pw, c / ow, c % ow);
+    const size_t g = (size_t)i * cells + c;
+    if (device_noise) {
+      // u0 < 0.03: += U(0.2, 10); u2 < 0.8: = -1
+      F4 a = rng_block(B.rng_seed, B.env_index_base + i, agx::step_index(B), RNG_RADAR_NOISE, c);
+      if (a.v[0] < 0.03f) m += (10.0f - 0.2f) * a.v[1] + 0.2f;
+      if (a.v[2] < 0.8f) m = -1.0f;
+    } else {
+      if (noise_mask && noise_mask[g] == 1.0f) m += noise_val[g];
+      if (invalid_mask && invalid_mask[g] == 1.0f) m = -1.0f;
+    }
+    ds_out[g] = 1.0f / m;
+  }
+}
+
+// RADAR: the radar task's reward, which penalises backward where the LiDAR task's penalises forward vehicle-frame x velocity
+template <bool RADAR>
 __global__ void __launch_bounds__(256) k_reward_lidar_navigation(AgxEnvBuffers B, int n, const float *__restrict__ target,
                                                                   const float *__restrict__ target_yaw,
                                                                   const float *__restrict__ action,
@@ -157,7 +218,7 @@ __global__ void __launch_bounds__(256) k_reward_lidar_navigation(AgxEnvBuffers B
     float vdc_reward = ((vdc > 0.0f) ? rp[4] * vdc * reasonable_vel : -0.2f) * fminf(dist / 3.0f, 1.0f);
     float vel_mag_pen = exp_penalty(2.0f, 2.0f, fmaxf(vel_norm - 3.0f, 0.0f));
     float close_to_goal = 1.0f - exp_reward(1.0f, 2.0f, dist);
-    float neg_x_pen = exp_penalty(2.0f, 8.0f, fmaxf(v.x, 0.0f)) * close_to_goal;
+    float neg_x_pen = exp_penalty(2.0f, 8.0f, RADAR ? fminf(v.x, 0.0f) : fmaxf(v.x, 0.0f)) * close_to_goal;
     float vel_pen = vel_mag_pen + neg_x_pen;
     float low_vel = exp_reward(1.5f, 10.0f, vel_norm) + exp_reward(1.5f, 0.5f, vel_norm);
     float correct_yaw = exp_reward(2.0f, 0.2f, ye) + exp_reward(4.0f, 15.0f, ye);
@@ -254,6 +315,11 @@ __global__ void __launch_bounds__(256) k_obs_lidar_navigation(AgxEnvBuffers B, i
 
 using namespace agx;
 
+// 16-byte loads: every env's block must start on a 16-byte boundary (H W 12 bytes per env) and hold whole groups of four points
+static int image_vec4(int H, int W, const float *pointcloud) {
+  return ((H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(pointcloud) & 15u) == 0) ? 1 : 0;
+}
+
 extern "C" int agx_lidar_image_obs(const AgxEnvBuffers *B, int n, int H, int W, int pool_h, int pool_w, int low_row0,
                                    const float *pointcloud, const float *noise_mask, const float *noise_val,
                                    const float *max_mask, const float *low_mask, const float *low_val, int device_noise,
@@ -265,18 +331,32 @@ extern "C" int agx_lidar_image_obs(const AgxEnvBuffers *B, int n, int H, int W, 
   AGX_REQUIRE(!low_mask || low_val, "low_mask needs low_val");
   const size_t lds = ((size_t)H * W + 4) * sizeof(float);
   AGX_REQUIRE(lds <= 64 * 1024, "image too large for the LDS range buffer (%d x %d)", H, W);
-  // 16-byte loads: every env's block must start on a 16-byte boundary (H W 12 bytes per env) and hold whole groups of four points
-  const int vec4 = ((H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(pointcloud) & 15u) == 0) ? 1 : 0;
+  const int vec4 = image_vec4(H, W, pointcloud);
   hipLaunchKernelGGL(k_lidar_image_obs, dim3(n), dim3(256), lds, (hipStream_t)stream, *B, n, H, W, pool_h, pool_w, low_row0,
                      pointcloud, noise_mask, noise_val, max_mask, low_mask, low_val, device_noise, vec4, time_to_collision,
                      downsampled);
   return check_launch("agx_lidar_image_obs");
 }
 
-extern "C" int agx_reward_lidar_navigation(const AgxEnvBuffers *B, int n, const float *target, const float *target_yaw,
-                                           const float *action, const float *prev_action, const float *time_to_collision,
-                                           const float *rp, float cpf, float *pos_err, float *prev_pos_err, int episode_len,
-                                           int reset_on_collision, float *reward, void *stream) {
+extern "C" int agx_radar_image_obs(const AgxEnvBuffers *B, int n, int H, int W, int pool_h, int pool_w, const float *pointcloud,
+                                   const float *noise_mask, const float *noise_val, const float *invalid_mask, int device_noise,
+                                   float *time_to_collision, float *downsampled, void *stream) {
+  AGX_REQUIRE(B && B->state && n > 0, "bad arguments");
+  AGX_REQUIRE(H > 0 && W > 0 && pool_h > 0 && pool_w > 0 && H >= pool_h && W >= pool_w, "bad image / pool sizes");
+  AGX_REQUIRE(pointcloud && time_to_collision && downsampled, "null buffer");
+  AGX_REQUIRE(!noise_mask || noise_val, "noise_mask needs noise_val");
+  const size_t lds = ((size_t)H * W + 4) * sizeof(float);
+  AGX_REQUIRE(lds <= 64 * 1024, "image too large for the LDS range buffer (%d x %d)", H, W);
+  hipLaunchKernelGGL(k_radar_image_obs, dim3(n), dim3(256), lds, (hipStream_t)stream, *B, n, H, W, pool_h, pool_w, pointcloud,
+                     noise_mask, noise_val, invalid_mask, device_noise, image_vec4(H, W, pointcloud), time_to_collision, downsampled);
+  return check_launch("agx_radar_image_obs");
+}
+
+template <bool RADAR>
+static int reward_lidar_navigation(const char *what, const AgxEnvBuffers *B, int n, const float *target, const float *target_yaw,
+                                   const float *action, const float *prev_action, const float *time_to_collision, const float *rp,
+                                   float cpf, float *pos_err, float *prev_pos_err, int episode_len, int reset_on_collision,
+                                   float *reward, void *stream) {
   AGX_REQUIRE(B && n > 0, "bad arguments");
   AGX_REQUIRE(B->flag_parity == 0 || B->flag_parity == 1, "flag_parity must be 0 or 1");
   AGX_REQUIRE(target && target_yaw && action && prev_action && time_to_collision && rp && pos_err && prev_pos_err && reward,
@@ -287,10 +367,28 @@ extern "C" int agx_reward_lidar_navigation(const AgxEnvBuffers *B, int n, const 
   for (int c = 0; c < 22; ++c) R.rp[c] = rp[c];  // rp is a HOST pointer (22 config scalars)
   const float mult = (float)(1.0 + 2.0 * (double)cpf);  // MULTIPLICATION_FACTOR_REWARD is evaluated in double (:585)
   const int block = pick_block(n);
-  hipLaunchKernelGGL(k_reward_lidar_navigation, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n, target,
-                     target_yaw, action, prev_action, time_to_collision, R, cpf, mult, pos_err, prev_pos_err, episode_len,
+  hipLaunchKernelGGL(k_reward_lidar_navigation<RADAR>, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n,
+                     target, target_yaw, action, prev_action, time_to_collision, R, cpf, mult, pos_err, prev_pos_err, episode_len,
                      reset_on_collision, reward);
-  return check_launch("agx_reward_lidar_navigation");
+  return check_launch(what);
+}
+
+extern "C" int agx_reward_lidar_navigation(const AgxEnvBuffers *B, int n, const float *target, const float *target_yaw,
+                                           const float *action, const float *prev_action, const float *time_to_collision,
+                                           const float *rp, float cpf, float *pos_err, float *prev_pos_err, int episode_len,
+                                           int reset_on_collision, float *reward, void *stream) {
+  return reward_lidar_navigation<false>("agx_reward_lidar_navigation", B, n, target, target_yaw, action, prev_action,
+                                        time_to_collision, rp, cpf, pos_err, prev_pos_err, episode_len, reset_on_collision, reward,
+                                        stream);
+}
+
+extern "C" int agx_reward_radar_navigation(const AgxEnvBuffers *B, int n, const float *target, const float *target_yaw,
+                                           const float *action, const float *prev_action, const float *time_to_collision,
+                                           const float *rp, float cpf, float *pos_err, float *prev_pos_err, int episode_len,
+                                           int reset_on_collision, float *reward, void *stream) {
+  return reward_lidar_navigation<true>("agx_reward_radar_navigation", B, n, target, target_yaw, action, prev_action,
+                                       time_to_collision, rp, cpf, pos_err, prev_pos_err, episode_len, reset_on_collision, reward,
+                                       stream);
 }
 
 extern "C" int agx_obs_lidar_navigation(const AgxEnvBuffers *B, int n, const float *target, const float *target_yaw,

@@ -31,6 +31,7 @@ enum {
   RNG_TARGET = 9,       // counter word 1 = episode; 4 draws (target ratio xyz, target yaw) (agx_nav_target_reset)
   RNG_IMU = 8,          // counter word 1 = env step; block = 3 * sub-step + j   (agx_imu_update)
   RNG_E2E_OBS_NOISE = 10,  // counter word 1 = env step; 12 draws -> 12 normals    (agx_end_to_end_obs, agx_post_step_end_to_end)
+  RNG_RADAR_NOISE = 11,  // counter word 1 = env step; block = pooled cell       (agx_radar_image_obs)
   RNG_ASSETS = 16,      // + asset index (< 2^16 assets)
   RNG_SENSOR_MOUNT = 1 << 16,  // + sensor index; counter word 1 = episode; 6 draws  (agx_sensor_mount_reset)
   RNG_DISTURB = 1 << 20 // + sub-step; counter word 1 = env step

@@ -12,6 +12,7 @@ from ..config.robot_config import (
     BaseQuadWithLidarCfg,
     BaseQuadWithStereoCameraCfg,
     LMF2Cfg,
+    LMF2RadarCfg,
     LMF2With64x48CameraCfg,
     MagpieCfg,
     TinyPropCfg,
@@ -32,5 +33,6 @@ robot_registry.register("base_quadrotor_with_imu", BaseMultirotor, BaseQuadWithI
 robot_registry.register("base_quadrotor_with_camera_imu", BaseMultirotor, BaseQuadWithCameraImuCfg)
 robot_registry.register("lmf2", BaseMultirotor, LMF2Cfg)
 robot_registry.register("lmf2_with_camera_64x48", BaseMultirotor, LMF2With64x48CameraCfg)
+robot_registry.register("lmf2_radar", BaseMultirotor, LMF2RadarCfg)  # robots/__init__.py:52 of the reference: the radar task's robot
 robot_registry.register("base_quad_root_link_control", BaseMultirotor, BaseQuadRootLinkControlCfg)
 robot_registry.register("tinyprop", BaseMultirotor, TinyPropCfg)  # robots/__init__.py of the reference: the end-to-end task's airframe

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 16
+#define AGX_ABI_VERSION 17
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -395,6 +395,29 @@ int agx_lidar_image_obs(const AgxEnvBuffers *buf, int num_envs, int height, int 
  * rp: HOST pointer to the 22 reward parameters in the order of lidar_navigation_task_config.py:30-53;
  * target [3][N], target_yaw [N], pos_err / prev_pos_err [3][N].                                  */
 int agx_reward_lidar_navigation(const AgxEnvBuffers *buf, int num_envs, const float *target,
+                                const float *target_yaw, const float *action,
+                                const float *prev_action, const float *time_to_collision,
+                                const float *rp, float curriculum_progress, float *pos_err,
+                                float *prev_pos_err, int episode_len, int reset_on_collision,
+                                float *reward, void *stream);
+
+/* ---- Radar navigation task (task/radar_navigation_task/radar_navigation_task.py), a subclass of the LiDAR
+ * task: its process_image_observation (:24-63) + add_noise_to_downsampled_lidar_data (:6-21).  Ranges,
+ * time_to_collision and the pool_h x pool_w min-pooling as in agx_lidar_image_obs (the same point pass);
+ * then, per pooled cell: m += noise_val where noise_mask == 1, m = -1 where invalid_mask == 1,
+ * downsampled = 1 / m (an invalid cell reads -1, a valid one lies in [1/20, 5]).  device_noise = 0: the
+ * three tensors ([N][cells]; 0/1 masks as floats; a NULL pointer = no such mask) reproduce the reference's
+ * torch draws; device_noise = 1: device generator, stream RNG_RADAR_NOISE of (env, buf->step_counter), one
+ * block per cell: u0 < 0.03 -> m += 9.8 u1 + 0.2; u2 < 0.8 -> m = -1.                                   */
+int agx_radar_image_obs(const AgxEnvBuffers *buf, int num_envs, int height, int width, int pool_h,
+                        int pool_w, const float *pointcloud, const float *noise_mask,
+                        const float *noise_val, const float *invalid_mask, int device_noise,
+                        float *time_to_collision, float *downsampled, void *stream);
+
+/* agx_reward_lidar_navigation with the radar task's compute_reward (:179-342): negative_x_vel_penalty
+ * takes clamp(v_x, max = 0) (:242-246) instead of clamp(v_x, min = 0); everything else, the truncation and
+ * the reset set are the same code.  rp in the order of radar_navigation_task_config.py:30-53.            */
+int agx_reward_radar_navigation(const AgxEnvBuffers *buf, int num_envs, const float *target,
                                 const float *target_yaw, const float *action,
                                 const float *prev_action, const float *time_to_collision,
                                 const float *rp, float curriculum_progress, float *pos_err,

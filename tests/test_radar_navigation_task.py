@@ -1,0 +1,183 @@
+"""CPU: the radar navigation task -- registry, configs and the `aerial_gym` alias, the unchanged parameter block of its robot, and the
+numpy restatement the GPU tests compare against (tests/radar_ref.py) pinned to the reference's own code through
+tests/golden/radar_*.npz and tests/golden/radar_cr/ (tests/golden_gen/gen_golden_radar_nav.py)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import radar_ref as R
+from conftest import GOLDEN, ROOT, rel_err
+
+NAME = "radar_navigation_task"
+FIXTURES = ("radar_reward", "radar_image_obs", "radar_config")
+
+
+def load_golden(name, cr=False):
+    """cr=True: the fixture made by the reference's code with correctly rounded elementary functions (tests/golden/radar_cr/)"""
+    return np.load(os.path.join(GOLDEN, *(["radar_cr"] if cr else []), name + ".npz"))
+
+
+def reward_of(g, radar=True):
+    return R.reward(g["pos_err"], g["vveh"], g["wbody"], g["yaw_error"], g["crashes"], g["action"], g["prev_action"], g["time_to_collision"],
+                    float(g["curriculum_progress"]), g["rp"], radar=radar)
+
+
+def images_of(orc, g):
+    pc = np.ascontiguousarray(g["pointcloud"][:, 0])
+    clean = R.image_obs(orc, pc, g["robot_position"], g["robot_linvel"])
+    noisy = R.image_obs(orc, pc, g["robot_position"], g["robot_linvel"], g["noise_mask"], g["noise_val"], g["invalid_mask"])
+    return clean, noisy
+
+
+def same_values(mine, ref, path=""):
+    """every value of the reference's (nested) table equals the attribute of the same name here"""
+    for key, value in ref.items():
+        if isinstance(value, dict) and set(value) == {"class"}:
+            assert getattr(mine, key).__name__ == value["class"], path + key
+        elif isinstance(value, dict) and isinstance(getattr(mine, key), type):
+            same_values(getattr(mine, key), value, path + key + ".")
+        else:
+            got = getattr(mine, key)
+            assert (list(got) if isinstance(got, tuple) else got) == value, (path + key, got, value)
+
+
+def test_names_resolve_and_configs_equal_the_reference():
+    import aerial_gym_simulator_amd as ag
+    from aerial_gym.config.robot_config.lmf2_radar_config import LMF2RadarCfg
+    from aerial_gym.config.sensor_config.lidar_config.fake_radar_config import fake_radar_config
+    from aerial_gym.config.task_config.radar_navigation_task_config import task_config
+    from aerial_gym.registry.robot_registry import robot_registry
+    from aerial_gym.registry.task_registry import task_registry
+
+    import aerial_gym_simulator_amd.config.robot_config as rc
+    import aerial_gym_simulator_amd.config.sensor_config as sc
+    import aerial_gym_simulator_amd.config.task_config as tc
+    from aerial_gym_simulator_amd.task.lidar_navigation_task import LiDARNavigationTask
+    from aerial_gym_simulator_amd.task.radar_navigation_task import RadarNavigationTask
+
+    assert task_config is tc.radar_navigation_task_config is ag.task_registry.get_task_config(NAME)
+    assert task_registry.get_task_class(NAME) is RadarNavigationTask and issubclass(RadarNavigationTask, LiDARNavigationTask)
+    assert LMF2RadarCfg is rc.LMF2RadarCfg is robot_registry.get_robot_config("lmf2_radar")
+    assert fake_radar_config is sc.fake_radar_config is LMF2RadarCfg.sensor_config.lidar_config
+    g = load_golden("radar_config")
+    ref = json.loads(str(g["config"]))
+    same_values(task_config, {k: v for k, v in ref["task"].items() if k != "vae_config"})
+    assert ref["task"]["vae_config"]["use_vae"] is False  # (its other entries configure the encoder that is then not built)
+    same_values(fake_radar_config, ref["sensor"])
+    for block in ("sensor_config", "init_config", "disturbance", "control_allocator_config"):
+        same_values(getattr(LMF2RadarCfg, block), {k: v for k, v in ref["robot"][block].items() if k not in ("camera_config", "imu_config")},
+                    block + ".")
+    # what the config states in this package's own terms
+    assert task_config.lidar_pool == (3, 6) and task_config.vae_config.use_vae is False
+    assert task_config.REWARD_PARAMETER_ORDER == tc.lidar_navigation_task_config.REWARD_PARAMETER_ORDER and len(task_config.REWARD_PARAMETER_ORDER) == 22
+    assert task_config.reward_parameters is not tc.lidar_navigation_task_config.reward_parameters
+    fn = task_config.action_transformation_function
+    assert fn.agx_kind == (2, 4)
+    import torch
+
+    out = fn(torch.from_numpy(g["action_transform_in"]))
+    assert np.array_equal(out.numpy(), g["action_transform_out"]) and np.abs(g["action_transform_in"]).max() > 1  # the clamp included
+
+
+def test_lmf2_radar_has_the_parameter_block_of_lmf2():
+    import hashlib
+
+    import aerial_gym_simulator_amd  # noqa: F401
+    from aerial_gym_simulator_amd.config.controller_config import lmf2_controller_config
+    from aerial_gym_simulator_amd.config.robot_config import LMF2Cfg, LMF2RadarCfg
+    from aerial_gym_simulator_amd.config.sim_config import BaseSimConfig
+    from aerial_gym_simulator_amd.robots.robot_model import pack_robot_params, robot_params_dict
+
+    for ctrl_cfg, ctrl in ((None, "none"), (lmf2_controller_config, "acceleration")):
+        a = bytes(pack_robot_params(robot_params_dict(LMF2Cfg, ctrl_cfg, ctrl, BaseSimConfig)))
+        b = bytes(pack_robot_params(robot_params_dict(LMF2RadarCfg, ctrl_cfg, ctrl, BaseSimConfig)))
+        assert a == b, ctrl
+    # (the hash tests/test_end_to_end_task.py records for lmf2)
+    assert hashlib.sha256(bytes(pack_robot_params(robot_params_dict(LMF2RadarCfg, None, "none", BaseSimConfig)))).hexdigest() == \
+        "15a95100b11eed2e0276d497a31517d5556bcaffc308ef5cee08773e3f25cf67"
+    own = {k for k in vars(LMF2RadarCfg) if not k.startswith("__")}
+    assert own == {"sensor_config"}  # lmf2_radar_config.py differs from lmf2_config.py in the sensor block alone
+
+
+def test_make_task_builds_the_radar_recipe():
+    import aerial_gym_simulator_amd as ag
+
+    cfg = ag.task_registry.get_task_config(NAME)
+    keys = ("seed", "num_envs", "headless", "device", "use_warp", "args")
+    old = {k: getattr(cfg, k) for k in keys}
+    try:
+        cfg.device = "cpu"
+        t = ag.task_registry.make_task(NAME, num_envs=4, headless=True)
+    finally:
+        for k, v in old.items():
+            setattr(cfg, k, v)
+    assert t.sim_env.robot_name == "lmf2_radar" and t.sim_env.controller_name == "lmf2_acceleration_control"
+    assert tuple(t.obs_dict["depth_range_pixels"].shape) == (4, 1, 48, 120, 3) and tuple(t.task_obs["observations"].shape) == (4, 337)
+    assert tuple(t.downsampled_lidar_data.shape) == (4, 320) and t._action_kind == (2, 4) and t._noise is None
+
+
+def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit(orc):
+    g = load_golden("radar_reward", cr=True)
+    assert np.array_equal(reward_of(g), g["reward"]) and np.array_equal(reward_of(g, radar=False), g["reward_lidar_formula"])
+    g = load_golden("radar_image_obs", cr=True)
+    clean, noisy = images_of(orc, g)
+    assert np.array_equal(clean[0], g["clean_ttc"]) and np.array_equal(clean[1], g["clean_ds"])
+    assert np.array_equal(noisy[0], g["noisy_ttc"]) and np.array_equal(noisy[1], g["noisy_ds"])
+
+
+def test_restatement_against_the_plain_torch_reference(orc):
+    """the bounds of the parent's tests (tests/test_gpu_lidar_nav.py): 1e-5 on the reward, 2e-6 on the image"""
+    g = load_golden("radar_reward")
+    err = rel_err(reward_of(g), g["reward"])
+    print("radar reward restatement vs plain torch:", err)
+    assert err < 1e-5
+    g = load_golden("radar_image_obs")
+    clean, noisy = images_of(orc, g)
+    errs = [rel_err(clean[0], g["clean_ttc"]), rel_err(clean[1], g["clean_ds"]), rel_err(noisy[0], g["noisy_ttc"]), rel_err(noisy[1], g["noisy_ds"])]
+    print("radar image restatement vs plain torch (ttc, image, noisy ttc, noisy image):", errs)
+    assert max(errs) < 2e-6
+
+
+@pytest.mark.parametrize("cr", [False, True])
+def test_goldens_are_what_they_claim(cr):
+    g = load_golden("radar_reward", cr=cr)
+    n = g["reward"].shape[0]
+    dist = np.linalg.norm(g["pos_err"], axis=1)
+    assert n == 768 and (g["vveh"][:, 0] > 0).sum() >= 200 and (g["vveh"][:, 0] < 0).sum() >= 200
+    assert (dist < 1).sum() >= 50 and ((dist > 1) & (dist < 3)).sum() >= 50 and (dist > 3).sum() >= 50
+    assert 30 <= g["crashes"].sum() <= 150 and (g["reward"][g["crashes"]] == g["rp"][21]).all()
+    assert (g["reward"] != g["reward_lidar_formula"]).sum() >= 200
+    g = load_golden("radar_image_obs", cr=cr)
+    assert g["pointcloud"].shape == (6, 1, 48, 120, 3) and g["noisy_ds"].shape == (6, 320)
+    nm, im = g["noise_mask"].reshape(6, 320) == 1, g["invalid_mask"].reshape(6, 320) == 1
+    assert (nm & ~im).sum() >= 5 and (nm & im).sum() >= 20 and abs(im.mean() - 0.8) <= 0.05
+    assert np.array_equal(g["noisy_ds"] == -1.0, im) and (g["noisy_ds"][nm & ~im] != g["clean_ds"][nm & ~im]).all()
+    assert np.array_equal(g["noisy_ds"][~nm & ~im], g["clean_ds"][~nm & ~im]) and np.array_equal(g["noisy_ttc"], g["clean_ttc"])
+    valid = g["noisy_ds"][~im]
+    assert valid.min() >= np.float32(1 / 20) and valid.max() <= 5.0 and g["clean_ds"].min() >= np.float32(0.1) and g["clean_ds"].max() <= 5.0
+    nv = g["noise_val"][g["noise_mask"] == 1]
+    assert nv.min() >= 0.2 and nv.max() <= 10.0 and not g["noise_val"][g["noise_mask"] == 0].any()
+    r = np.linalg.norm(g["pointcloud"][:, 0] - g["robot_position"][:, None, None, :], axis=-1)
+    assert (r < 0.2).any() and (r > 10).any() and not g["robot_linvel"][0].any() and g["clean_ttc"][0] == 10.0
+    for name in FIXTURES:
+        assert os.path.getsize(os.path.join(GOLDEN, *(["radar_cr"] if cr else []), name + ".npz")) < 460 * 1024, name
+
+
+@pytest.mark.parametrize("cr", [False, True])
+def test_generator_reproduces_the_committed_goldens(cr, tmp_path):
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ref_shells
+
+    if not ref_shells.reference_available():
+        pytest.skip("the reference tree is not on this machine")
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "golden_gen", "gen_golden_radar_nav.py"), "--out", str(tmp_path)] + (["--cr"] if cr else [])
+    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npz" for n in FIXTURES)
+    for name in FIXTURES:
+        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, cr=cr)
+        assert sorted(a.files) == sorted(b.files), name
+        for key in b.files:
+            assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (name, key)
