@@ -15,6 +15,7 @@ MAX_ACTIONS = 8
 MAX_SUBSTEPS = 32
 MAX_BODIES = 24
 LAUNCH_LEAN, LAUNCH_BODY_WRENCH = 4, 8  # AgxEnvBuffers.launch_flags bits 2 and 3
+LAUNCH_ROV = 0x10000  # bit 16: the robot kind BaseROV (AGX_LAUNCH_ROV)
 
 CTRL_IDS = {
     "none": 0,
@@ -291,7 +292,7 @@ class AgxEndToEndReward(C.Structure):
                 ("diff_gain", C.c_float), ("diff_exp", C.c_float), ("divisor", C.c_float)]
 
 
-ABI_VERSION = 17  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 18  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),

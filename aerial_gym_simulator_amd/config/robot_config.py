@@ -1,6 +1,6 @@
 """Robot configs: base_quadrotor and base_octarotor
 (aerial_gym/config/robot_config/base_quad_config.py, base_octarotor_config.py) plus the URDF
-constants of resources/robots/{quad,octarotor}/*.urdf as data (``robot_model``); magpie, lmf2, tinyprop the same way."""
+constants of resources/robots/{quad,octarotor}/*.urdf as data (``robot_model``); magpie, lmf2, tinyprop, base_rov the same way."""
 import numpy as np
 
 from .sensor_config import (
@@ -220,6 +220,75 @@ class BaseOctarotorWithLidar32x512Cfg(BaseOctarotorCfg):
     class sensor_config(BaseOctarotorCfg.sensor_config):
         enable_lidar = True
         lidar_config = Lidar32x512Config
+
+
+class BaseROVCfg:  # base_rov_config.py:14-241, resources/robots/BlueROV/rov.urdf -- the robot of examples/position_control_example_rov.py
+    """The reference's fully actuated ROV (robots/base_rov.py: BaseROV).  Its URDF is the octarotor's with another visual mesh: a
+    0.3 kg base link, eight massless arm links half way out and eight 0.1 kg thruster links at (+-s, +-s, +-s), s = 0.1732 m,
+    posed with xyz AND rpy -- a thruster pushes along its link's z axis, at the link's position.  All four drag coefficient
+    triples are zero as in the reference; the class that reads them (BaseROV) applies the quadratic linear term per axis.
+    Pinned by tests/golden/robot_base_rov.npz (composite of the reference's URDF)."""
+
+    class init_config:
+        min_init_state = [0.0, 0.0, 0.0, 0, 0, -_PI, 1.0, -0.2, -0.2, -0.2, -0.2, -0.2, -0.2]
+        max_init_state = [1.0, 1.0, 1.0, 0, 0, _PI, 1.0, 0.2, 0.2, 0.2, 0.2, 0.2, 0.2]
+
+    class sensor_config:
+        enable_camera = False
+        camera_config = BaseDepthCameraConfig
+        enable_lidar = False
+        lidar_config = BaseLidarConfig
+        enable_imu = False
+        imu_config = BaseImuConfig
+
+    class damping:  # along the body x, y, z axes
+        linvel_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        linvel_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+
+    class disturbance:
+        enable_disturbance = True
+        prob_apply_disturbance = 0.05
+        max_force_and_torque_disturbance = [1.5, 1.5, 1.5, 0.25, 0.25, 0.25]
+
+    class robot_asset(_CommonAsset):
+        file = "rov.urdf"
+        name = "base_rov"
+        angular_damping = 0.0000001
+        linear_damping = 0.0000001
+
+    class robot_model:  # resources/robots/BlueROV/rov.urdf
+        base_mass = 0.3
+        base_inertia = [[0.048000000000000015, 0, 0], [0, 0.048000000000000015, 0], [0, 0, 0.048000000000000015]]
+        collision_sphere_radius = 0.30000000000000004
+        motor_mass = 0.1
+        motor_xyz = [[sx * _S, sy * _S, sz * _S] for sz in (1, -1) for sy in (1, -1) for sx in (1, -1)]
+        motor_rpy = _OCTA_RPY + _OCTA_RPY[::-1]
+
+    class control_allocator_config:
+        num_motors = 8
+        force_application_level = "motor_link"
+        application_mask = [1 + 8 + i for i in range(8)]
+        motor_directions = [1, -1, 1, -1, 1, -1, 1, -1]
+        allocation_matrix = [
+            [-0.78867513, 0.21132487, -0.21132487, 0.78867513, 0.78867513, -0.21132487, 0.21132487, -0.78867513],
+            [0.21132487, 0.78867513, -0.78867513, -0.21132487, -0.21132487, -0.78867513, 0.78867513, 0.21132487],
+            [0.57735027, -0.57735027, -0.57735027, 0.57735027, 0.57735027, -0.57735027, -0.57735027, 0.57735027],
+            [0.14226497, -0.21547005, 0.25773503, 0.01547005, -0.01547005, -0.25773503, 0.21547005, -0.14226497],
+            [-0.25773503, 0.01547005, 0.14226497, 0.21547005, -0.21547005, -0.14226497, -0.01547005, 0.25773503],
+            [0.11547005, -0.23094011, -0.11547005, 0.23094011, -0.23094011, 0.11547005, 0.23094011, -0.11547005],
+        ]
+
+        class motor_model_config:
+            use_rps = False
+            motor_thrust_constant_min, motor_thrust_constant_max = 0.00000926312, 0.00001826312
+            motor_time_constant_increasing_min, motor_time_constant_increasing_max = 0.01, 0.03
+            motor_time_constant_decreasing_min = motor_time_constant_decreasing_max = 0.005
+            max_thrust, min_thrust = 6.25, -6.25
+            max_thrust_rate = 100000.0
+            thrust_to_torque_ratio = 0.01
+            use_discrete_approximation = True
 
 
 class MagpieCfg:  # magpie_config.py:15-176, resources/robots/magpie/model.urdf

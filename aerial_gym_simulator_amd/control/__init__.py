@@ -46,3 +46,8 @@ controller_registry.register_controller(
 controller_registry.register_controller(
     "rov_fully_actuated_control", FullyActuatedController, fully_actuated_controller_config
 )
+# examples/position_control_example_rov.py of the reference asks for this name, which the reference itself never registers (its
+# control/__init__.py:98-100 has the `rov_` name only): the same class and config under it, so that the example's call builds
+controller_registry.register_controller(
+    "fully_actuated_control", FullyActuatedController, fully_actuated_controller_config
+)

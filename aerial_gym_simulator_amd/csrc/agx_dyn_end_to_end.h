@@ -299,6 +299,7 @@ extern "C" int agx_post_step_end_to_end(const AgxRobotParams *P, const AgxEnvBuf
   AGX_REQUIRE(target && obs && actions && prev_actions && prev_pos_error && B->state && B->derived, "agx_post_step_end_to_end: null buffer");
   AGX_REQUIRE(!B->step_rows[0] && !B->step_rows[1], "agx_post_step_end_to_end: exchange rows (step_rows) are not written for the 15-D observation");
   AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_LEAN) == 0, "agx_post_step_end_to_end: the observation reads robot_body_angvel, which the lean step does not maintain");
+  AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_ROV) == 0, "AGX_LAUNCH_ROV: agx_post_step_end_to_end resets multirotors only (use agx_reset_masked)");
   AGX_REQUIRE(e2e_aligned16(actions) && e2e_aligned16(prev_actions), "agx_post_step_end_to_end: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   AGX_DISPATCH_M(P->num_motors, hipLaunchKernelGGL((k_e2e_post_step<kM>), dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *P,

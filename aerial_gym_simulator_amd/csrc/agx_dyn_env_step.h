@@ -1,5 +1,6 @@
 #pragma once
-// The one-lane-per-env step kernel k_env_step<M, CTRL, SINGLE, WIDE> (108 instances) and the occupancy it is compiled for.
+// The one-lane-per-env step kernel k_env_step<M, CTRL, SINGLE, WIDE> (108 instances), its ROV kind k_env_step_rov<CTRL, SINGLE, WIDE>
+// (12 instances) and the occupancy they are compiled for.
 // Part of the one translation unit agx_dynamics.hip, which alone includes it (after the AGX_DYN_* switches).
 
 namespace agx {
@@ -19,211 +20,22 @@ constexpr int env_step_single_waves(int M, int CTRL) {
              ? AGX_DYN_WAVES_LEAN_LAWS
              : (CTRL == AGX_CTRL_ACCELERATION ? 2 : AGX_DYN_WAVES);  // (the acceleration law: 168-181 VGPRs, spills at 3 waves)
 }
+// (the body: agx_dyn_env_step_body.h, shared as text with k_env_step_rov below)
 template <int M, int CTRL, bool SINGLE, bool WIDE>
 __global__ void __launch_bounds__(WIDE ? 64 : 256, WIDE ? 1 : (SINGLE ? env_step_single_waves(M, CTRL) : AGX_DYN_WAVES_LOOP))
     k_env_step(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, int k_arg, AgxTaskArgs T) {
-  const int k = SINGLE ? 1 : k_arg;
-  extern __shared__ float traj[];  // [k][3][blockDim] sub-step positions (only with obstacles)
-  const int tid = threadIdx.x, bd = blockDim.x;
-  const int i = blockIdx.x * bd + tid;
-  bool reset = false;
-  // peer push: one wave holds the step until the slot of its rows is free (flags loaded here, looked at when the kernel is done)
-  if (blockIdx.x == 0 && tid < 64) push_publish_previous(B);
-  const uint32_t push_peek = (blockIdx.x == 0 && tid < 64) ? push_wait_peek(B) : 0u;
-  if (i < n) {
-    const int A = P.num_actions;
-    // AGX_LAUNCH_LEAN (launch_flags bit 2): the tensors that only exist to be LOOKED AT through the tensor dict are not
-    // maintained -- Euler angles, vehicle-frame quaternion / velocity, robot_actions / robot_prev_actions (40 + 48 of the
-    // 330 bytes an env moves per step); the body-frame velocities stay (the observation kernel reads them)
-    const bool lean = (B.launch_flags & 4) != 0;
-    EnvState s = load_state(B.state, n, i);
-    float u[M], kT[M], tinc[M], tdec[M];
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      u[j] = AGX_AT(B.motor_thrust, j);
-      kT[j] = P.use_rps ? AGX_AT(B.motor_kT, j) : 1.0f;
-      tinc[j] = B.motor_tau_inc ? AGX_AT(B.motor_tau_inc, j) : P.tau_inc_uniform;
-      tdec[j] = B.motor_tau_dec ? AGX_AT(B.motor_tau_dec, j) : P.tau_dec_uniform;
-    }
-    // EXTERNAL controller (a user class evaluated by the host between launches): actions_in is ITS OUTPUT, the body
-    // wrench [N][6]; robot_actions / robot_prev_actions (A columns) are maintained by the host and only read here
-    constexpr bool EXT = CTRL == AGX_CTRL_WRENCH;
-    float a_in[AGX_MAX_ACTIONS], a_old[AGX_MAX_ACTIONS];
-    // (the row index in 32 bits: n x 8 actions < 2^32.  The 64-bit multiply the compiler made of (size_t)i * A carried a
-    // don't-care register into its high half -- one a state load was still writing -- and waited for that load first)
-    const unsigned arow = (unsigned)i * (unsigned)(EXT ? 6 : A);
-#pragma unroll
-    for (int c = 0; c < AGX_MAX_ACTIONS; ++c) {
-      a_in[c] = (c < (EXT ? 6 : A)) ? actions_in[arow + (unsigned)c] : 0.0f;
-      a_old[c] = (c < A && !lean) ? AGX_AT(B.actions, c) : 0.0f;
-    }
-    Derived d{};
-    if (k == 0 && T.kind != AGX_TASK_NONE) d = load_derived(B.derived, n, i);
-    // What the bookkeeping / task epilogue reads is requested HERE, with the state.  Behind the stores of this kernel the
-    // compiler cannot move a load up (the buffers may alias for all it knows), and each load issued down there is a memory
-    // round trip of its own on the wave's critical path that also sits out every store in front of it (gfx9 counts loads and
-    // stores in one vmcnt): step counter -> target -> previous error were three such trips per wave.
-    const bool more_launches = (B.launch_flags & 2) != 0;  // (launch_flags: see below)
-    const bool task_epilogue = T.kind != AGX_TASK_NONE && !more_launches;
-    const int steps_in = B.sim_steps[i];
-    const int crashed_in = (B.launch_flags & 1) ? B.crashes[i] : 0;
-    V3 tgt{0, 0, 0}, ppe{0, 0, 0};
-    if (task_epilogue) {
-      tgt = V3{AGX_AT(T.target, 0), AGX_AT(T.target, 1), AGX_AT(T.target, 2)};
-      if (T.kind != AGX_TASK_POSITION) ppe = V3{AGX_AT(T.pos_err, 0), AGX_AT(T.pos_err, 1), AGX_AT(T.pos_err, 2)};
-    }
-    float a_prev_in[AGX_MAX_ACTIONS];  // robot_prev_actions as the last step left them (a k = 0 launch or an external controller reads them)
-#pragma unroll
-    for (int c = 0; c < AGX_MAX_ACTIONS; ++c) a_prev_in[c] = ((k == 0 || EXT) && c < A && !lean) ? AGX_AT(B.prev_actions, c) : 0.0f;
-    // the gains LAST: with uniform gains (B.gains null) the registers they are moved into are the ones the other arm loads into,
-    // and the compiler waits for every load in flight before the move -- behind the last load that wait costs nothing
-    Gains g{};
-    if (CTRL != AGX_CTRL_NONE && CTRL != AGX_CTRL_WRENCH) g = B.gains ? load_gains(B.gains, n, i) : uniform_gains(P);
-    Wrench wc{V3{0, 0, 0}, V3{0, 0, 0}};
-    const bool root_link = P.root_link_mode != 0;
-    const int sub_base = (B.launch_flags >> 8) & 0xFF;  // physics sub-step this launch starts at (split env steps)
-    bool has_drag = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      has_drag = has_drag || P.lin_drag_linear[c] != 0.0f || P.lin_drag_quadratic[c] != 0.0f || P.ang_drag_linear[c] != 0.0f ||
-                 P.ang_drag_quadratic[c] != 0.0f;
-    V3 tlo = s.p, thi = s.p;
-    constexpr bool kLawReadsNoAngles = CTRL == AGX_CTRL_POSITION || CTRL == AGX_CTRL_FULLY_ACTUATED || CTRL == AGX_CTRL_NONE || CTRL == AGX_CTRL_WRENCH;
-    for (int sub = 0; sub < k; ++sub) {
-      d = (kLawReadsNoAngles && lean) ? update_states_lean(s) : update_states(s);
-      float a[AGX_MAX_ACTIONS];
-#pragma unroll
-      for (int c = 0; c < AGX_MAX_ACTIONS; ++c) a[c] = clamp_minmax(a_in[c], -10.0f, 10.0f);  // clip_actions
-      // EXTERNAL ROBOT (AGX_LAUNCH_BODY_WRENCH, host-evaluated robot.step()): actions_in is the net body wrench itself
-      const bool body_wrench = EXT && (B.launch_flags & AGX_LAUNCH_BODY_WRENCH) != 0;  // wave-uniform
-      if (CTRL == AGX_CTRL_NONE) {
-#pragma unroll
-        for (int j = 0; j < M; ++j) u[j] = motor_update(P, a[j], u[j], kT[j], tinc[j], tdec[j]);
-      } else if (!body_wrench) {
-        if (EXT) wc = Wrench{V3{a_in[0], a_in[1], a_in[2]}, V3{a_in[3], a_in[4], a_in[5]}};  // as handed in, not clipped
-      else wc = run_controller<CTRL>(P, s, d, a, g);
-        const float w6[6] = {wc.f.x, wc.f.y, wc.f.z, wc.t.x, wc.t.y, wc.t.z};
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          float r = 0.0f;
-#pragma unroll
-          for (int c = 0; c < 6; ++c) r += P.alloc_pinv[6 * j + c] * w6[c];
-          u[j] = motor_update(P, r, u[j], kT[j], tinc[j], tdec[j]);
-        }
-      }
-      float bw[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < M; ++j) acc += (root_link ? P.alloc[M * r + j] : P.wrench_map[M * r + j]) * u[j];
-        bw[r] = body_wrench ? a_in[r] : acc;
-      }
-      // The ROOT link's entry of robot_force / robot_torque_tensor: the allocator's wrench in root-link mode, else 0.
-      // simulate_drag (base_multirotor.py:260-285; pre-physics body velocities) and apply_disturbance (:213-234) accumulate
-      // into it with `+=`, in that order; the net wrench on the rigid composite is the motor links' sum plus that entry.  So
-      // with forces at the motor links, drag AND disturbance are summed first and added to the links' sum once (`root`);
-      // with one of the two, or in root-link mode, that is the running sum below.  All-zero drag coefficients (base
-      // quadrotor) add +-0 to every component: skipped (a scalar test of kernel arguments).
-      // (The same drag and disturbance arithmetic as in k_robot_step, agx_dyn_robot.h: written out in both)
-      const bool any_dist = !body_wrench && (B.disturb != nullptr || B.disturb_prob > 0.0f);
-      const bool split_root = !root_link && has_drag && any_dist;  // wave-uniform
-      float dr[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, di[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (has_drag) {
-        float vbn = norm(d.vbody);
-        dr[0] = (-P.lin_drag_linear[0] * d.vbody.x) + (-P.lin_drag_quadratic[0] * vbn * d.vbody.x);
-        dr[1] = (-P.lin_drag_linear[1] * d.vbody.y) + (-P.lin_drag_quadratic[1] * vbn * d.vbody.y);
-        dr[2] = (-P.lin_drag_linear[2] * d.vbody.z) + (-P.lin_drag_quadratic[2] * vbn * d.vbody.z);
-        dr[3] = (-P.ang_drag_linear[0] * d.wbody.x) + (-P.ang_drag_quadratic[0] * fabsf(d.wbody.x) * d.wbody.x);
-        dr[4] = (-P.ang_drag_linear[1] * d.wbody.y) + (-P.ang_drag_quadratic[1] * fabsf(d.wbody.y) * d.wbody.y);
-        dr[5] = (-P.ang_drag_linear[2] * d.wbody.z) + (-P.ang_drag_quadratic[2] * fabsf(d.wbody.z) * d.wbody.z);
-      }
-      if (B.disturb) {  // draws supplied by the host
-        const float *dd = B.disturb + (size_t)(sub_base + sub) * 7 * n + i;
-        float occ = dd[0];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          float lo = -B.disturb_max[c], hi = B.disturb_max[c];
-          di[c] = ((hi - lo) * dd[(size_t)(1 + c) * n] + lo) * occ;
-        }
-      } else if (B.disturb_prob > 0.0f) {  // same, drawn in place: 7 uniforms per env and sub-step
-        float ud[7];
-        rng_fill<7>(B.rng_seed, B.env_index_base + i, agx::step_index(B), RNG_DISTURB + sub_base + sub, ud);
-        float occ = ud[0] < B.disturb_prob ? 1.0f : 0.0f;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          float lo = -B.disturb_max[c], hi = B.disturb_max[c];
-          di[c] = ((hi - lo) * ud[1 + c] + lo) * occ;
-        }
-      }
-      if (!body_wrench && (has_drag || any_dist)) {  // an absent term is +0: x + 0 = x
-#pragma unroll
-        for (int c = 0; c < 6; ++c) bw[c] = split_root ? bw[c] + (dr[c] + di[c]) : (bw[c] + dr[c]) + di[c];
-      }
-      if (B.body_force && sub == k - 1) {  // what the IMU's force sensor sees (agx_imu_update)
-        AGX_AT(B.body_force, 0) = bw[0]; AGX_AT(B.body_force, 1) = bw[1]; AGX_AT(B.body_force, 2) = bw[2];
-      }
-      integrate(P, s, V3{bw[0], bw[1], bw[2]}, V3{bw[3], bw[4], bw[5]});
-      if (B.boxes) {
-        traj[(sub * 3 + 0) * bd + tid] = s.p.x;
-        traj[(sub * 3 + 1) * bd + tid] = s.p.y;
-        traj[(sub * 3 + 2) * bd + tid] = s.p.z;
-        if (sub == 0) { tlo = s.p; thi = s.p; }
-        tlo = V3{fminf(tlo.x, s.p.x), fminf(tlo.y, s.p.y), fminf(tlo.z, s.p.z)};
-        thi = V3{fmaxf(thi.x, s.p.x), fmaxf(thi.y, s.p.y), fmaxf(thi.z, s.p.z)};
-      }
-    }
-    // EnvManager.reset_tensors + compute_observations (env_manager.py:342-344, 358-362)
-    // launch_flags (external controllers run ONE launch per physics sub-step): bit 0 = an earlier launch of this env
-    // step already ran: accumulate its crash flag; bit 1 = more launches follow: no step counter / truncation / task epilogue
-    bool crashed = crashed_in != 0;
-    if (B.boxes && k > 0) crashed = collide_trajectory(B.boxes, B.num_boxes, n, i, traj, k, bd, tid, tlo, thi, P.collision_radius) || crashed;
-    store_state(B.state, n, i, s);
-    if (k > 0) {
-      if (lean) store_body_velocities(B.derived, n, i, d);
-      else store_derived(B.derived, n, i, d);
-#pragma unroll
-      for (int j = 0; j < M; ++j) AGX_AT(B.motor_thrust, j) = u[j];
-      if (B.wrench_cmd) {
-        AGX_AT(B.wrench_cmd, 0) = wc.f.x; AGX_AT(B.wrench_cmd, 1) = wc.f.y; AGX_AT(B.wrench_cmd, 2) = wc.f.z;
-        AGX_AT(B.wrench_cmd, 3) = wc.t.x; AGX_AT(B.wrench_cmd, 4) = wc.t.y; AGX_AT(B.wrench_cmd, 5) = wc.t.z;
-      }
-    }
-    // RobotManagerIGE.pre_physics_step runs every sub-step: prev <- cur, cur <- action
-    float a_cur[AGX_MAX_ACTIONS], a_prev[AGX_MAX_ACTIONS];
-#pragma unroll
-    for (int c = 0; c < AGX_MAX_ACTIONS; ++c) {
-      a_cur[c] = (k > 0 && !EXT) ? a_in[c] : a_old[c];
-      a_prev[c] = (k >= 2 && !EXT) ? a_in[c] : ((k == 1 && !EXT) ? a_old[c] : a_prev_in[c]);
-      if (c < A && k > 0 && !EXT && !lean) {
-        AGX_AT(B.prev_actions, c) = a_prev[c];
-        AGX_AT(B.actions, c) = a_cur[c];
-      }
-    }
-    const int steps = steps_in + (more_launches ? 0 : 1);
-    if (!more_launches) B.sim_steps[i] = steps;
-    bool trunc = false;
-    if (task_epilogue) {
-      float rew;
-      if (T.kind == AGX_TASK_POSITION) {
-        rew = reward_position(s, d.qveh, d.wbody, tgt, crashed);
-      } else {
-        AGX_AT(T.prev_pos_err, 0) = ppe.x; AGX_AT(T.prev_pos_err, 1) = ppe.y; AGX_AT(T.prev_pos_err, 2) = ppe.z;
-        V3 pe = quat_rotate_inverse(d.qveh, tgt - s.p);
-        AGX_AT(T.pos_err, 0) = pe.x; AGX_AT(T.pos_err, 1) = pe.y; AGX_AT(T.pos_err, 2) = pe.z;
-        rew = reward_navigation(T.rp, T.curriculum_progress, pe, ppe, a_cur[0], a_cur[2], a_cur[3], a_prev[0], a_prev[2],
-                                a_prev[3], crashed);
-      }
-      T.reward[i] = rew;
-      trunc = steps > T.episode_len;
-      reset = (crashed && T.reset_on_collision) || trunc;
-      B.reset_mask[i] = reset ? 1 : 0;
-      if (T.successes) nav_bookkeeping_epilogue(T, i, true, tgt, s.p, crashed, trunc);  // (wave-uniform pointer test)
-    }
-    B.crashes[i] = crashed ? 1 : 0;
-    if (!more_launches) B.truncations[i] = trunc ? 1 : 0;
-  }
-  if (T.kind != AGX_TASK_NONE && __ballot(reset) != 0ull && (tid & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
-  if (blockIdx.x == 0 && tid < 64) push_wait_finish(B, push_peek);
+  constexpr bool ROV = false;
+#include "agx_dyn_env_step_body.h"
+}
+
+// The ROV kind of the same step (AGX_LAUNCH_ROV): eight thrusters under the fully actuated law, no_control or the external wrench --
+// the combinations an ROV can occur in (12 instances), compiled for the occupancy of the eight-motor multirotor instances.
+template <int CTRL, bool SINGLE, bool WIDE>
+__global__ void __launch_bounds__(WIDE ? 64 : 256, WIDE ? 1 : (SINGLE ? env_step_single_waves(8, CTRL) : AGX_DYN_WAVES_LOOP))
+    k_env_step_rov(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, int k_arg, AgxTaskArgs T) {
+  static_assert(CTRL == AGX_CTRL_FULLY_ACTUATED || CTRL == AGX_CTRL_NONE || CTRL == AGX_CTRL_WRENCH, "the laws that read no Euler angles");
+  constexpr int M = 8;
+  constexpr bool ROV = true;
+#include "agx_dyn_env_step_body.h"
 }
 }  // namespace agx

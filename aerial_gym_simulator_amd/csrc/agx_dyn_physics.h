@@ -17,6 +17,19 @@ AGX_DEV Derived update_states(const EnvState &s) {
   return d;
 }
 
+// BaseROV.update_states (base_rov.py:251-258; the robot kind AGX_LAUNCH_ROV): get_euler_xyz_tensor(q) is stored as it is, in
+// [0, 2 pi), without ssa(); the rest is the same.  (The laws an ROV runs read no Euler angles: kLawReadsNoAngles in the env step.)
+AGX_DEV Derived update_states_rov(const EnvState &s) {
+  Derived d;
+  V3 e = euler_xyz_0_2pi(s.q);
+  d.euler = e;
+  d.qveh = quat_from_yaw(e.z * 1.0f);
+  d.vveh = quat_rotate_inverse(d.qveh, s.v);
+  d.vbody = quat_rotate_inverse(s.q, s.v);
+  d.wbody = quat_rotate_inverse(s.q, s.w);
+  return d;
+}
+
 // The lean step (AGX_LAUNCH_LEAN) does not maintain Euler angles / vehicle-frame velocity, and under the laws that read neither
 // (position, fully actuated; no controller) does not EVALUATE them either: roll and pitch are two of the three float64
 // function evaluations of update_states.  What remains is what the task epilogue and the observation read, the same

@@ -16,7 +16,8 @@ struct ResetDraws {
 };
 
 // strict mode: the tensors torch drew (AoS, the reference's order)
-template <int M>
+// MOTORS = false (the ROV kind): BaseROV.reset_idx draws nothing for the motors, u_tau_inc .. u_kT may be NULL
+template <int M, bool MOTORS = true>
 AGX_DEV void host_reset_draws(const AgxRobotParams &P, const AgxResetArgs &R, int i, ResetDraws<M> &D) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -28,7 +29,7 @@ AGX_DEV void host_reset_draws(const AgxRobotParams &P, const AgxResetArgs &R, in
 #pragma unroll
   for (int c = 0; c < 12; ++c) D.ug[c] = R.randomize_gains ? R.u_gains[(size_t)i * 12 + c] : 0.0f;
 #pragma unroll
-  for (int j = 0; j < M; ++j) {
+  for (int j = 0; j < (MOTORS ? M : 0); ++j) {
     size_t k = (size_t)i * M + j;
     D.um[j][0] = R.u_tau_inc[k];
     D.um[j][1] = R.u_tau_dec[k];
@@ -42,9 +43,9 @@ AGX_DEV void host_reset_draws(const AgxRobotParams &P, const AgxResetArgs &R, in
 // the 9 + M blocks (10 rounds each) back to back, and with a few of 8192 envs resetting on almost every step that
 // serial chain was the longest path of the reset / observation kernel.  Same (seed; env, episode, stream, block)
 // coordinates, hence the same draws as rng_fill / rng_block in any other arrangement.  Must be called by all 64 lanes.
-template <int M>
+template <int M, bool MOTORS = true>
 AGX_DEV void wave_reset_draws(const AgxResetArgs &R, int i, int ep, bool mine, ResetDraws<M> &D) {
-  constexpr int NB = 9 + M;
+  constexpr int NB = 9 + (MOTORS ? M : 0);
   const int lane = threadIdx.x & 63;
   int stream = RNG_MOTOR, blk = lane - 9;
   if (lane < 2) { stream = RNG_BOUNDS; blk = lane; }
@@ -57,7 +58,7 @@ AGX_DEV void wave_reset_draws(const AgxResetArgs &R, int i, int ep, bool mine, R
       rng_fill<13>(R.seed, i, ep, RNG_STATE, D.us);
       if (R.randomize_gains) rng_fill<12>(R.seed, i, ep, RNG_GAINS, D.ug);
 #pragma unroll
-      for (int j = 0; j < M; ++j) {
+      for (int j = 0; j < (MOTORS ? M : 0); ++j) {
         F4 um = rng_block(R.seed, i, ep, RNG_MOTOR, j);
 #pragma unroll
         for (int k = 0; k < 4; ++k) D.um[j][k] = um.v[k];
@@ -86,7 +87,7 @@ AGX_DEV void wave_reset_draws(const AgxResetArgs &R, int i, int ep, bool mine, R
       for (int c = 0; c < 12; ++c) AGX_TAKE(D.ug[c], 6 + c / 4, c % 4)
     }
 #pragma unroll
-    for (int j = 0; j < M; ++j) {
+    for (int j = 0; j < (MOTORS ? M : 0); ++j) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) AGX_TAKE(D.um[j][k], 9 + j, k)
     }
@@ -126,7 +127,9 @@ AGX_DEV ResetValues<M> reset_env_values(const AgxRobotParams &P, const AgxResetA
   return V;
 }
 // ... and the stores
-template <int M>
+// MOTORS = false (the ROV kind): base_rov.py:171-198 does not call control_allocator.reset_idx -- motor thrusts and motor constants
+// of a resetting env stay exactly as they are
+template <int M, bool MOTORS = true>
 AGX_DEV void reset_env_store(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, int ep,
                              const ResetValues<M> &V) {
 #pragma unroll
@@ -140,7 +143,7 @@ AGX_DEV void reset_env_store(const AgxRobotParams &P, const AgxEnvBuffers &B, in
     for (int c = 0; c < 12; ++c) AGX_AT(B.gains, c) = V.gains[c];
   }
 #pragma unroll
-  for (int j = 0; j < M; ++j) {
+  for (int j = 0; j < (MOTORS ? M : 0); ++j) {
     if (B.motor_tau_inc) AGX_AT(B.motor_tau_inc, j) = V.mot[j][0];
     if (B.motor_tau_dec) AGX_AT(B.motor_tau_dec, j) = V.mot[j][1];
     AGX_AT(B.motor_thrust, j) = V.mot[j][2];
@@ -150,11 +153,11 @@ AGX_DEV void reset_env_store(const AgxRobotParams &P, const AgxEnvBuffers &B, in
   if (B.episode_count) B.episode_count[i] = ep + 1;
 }
 // returns the new state
-template <int M>
+template <int M, bool MOTORS = true>
 AGX_DEV EnvState reset_env(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, int ep,
                            const ResetDraws<M> &D) {
   const ResetValues<M> V = reset_env_values<M>(P, R, D);
-  reset_env_store<M>(P, B, n, R, i, ep, V);
+  reset_env_store<M, MOTORS>(P, B, n, R, i, ep, V);
   return V.s;
 }
 
@@ -162,7 +165,8 @@ AGX_DEV EnvState reset_env(const AgxRobotParams &P, const AgxEnvBuffers &B, int 
 // motor_model.py:140-154, env_manager.py:301) and, when WITH_OBS, the position task's observation of the post-reset state.
 // `any`: some env of the batch resets (wave-uniform); s / d: the env's state and derived tensors as the step left them.
 // Must be called by all 64 lanes (wave_reset_draws).
-template <int M, bool WITH_OBS>
+// ROV: BaseROV.reset_idx (base_rov.py:171-198) -- no motor draws, motor state untouched, Euler angles of the refresh without ssa().
+template <int M, bool WITH_OBS, bool ROV = false>
 AGX_DEV void reset_and_observe(const AgxRobotParams &P, const AgxEnvBuffers &B, int n, const AgxResetArgs &R, int i, bool valid,
                                bool any, bool mine, int ep, V3 tgt, float *__restrict__ obs, const EnvState &s, const Derived &d) {
   if (!any) {  // nobody resets: the reference does not touch anything
@@ -171,16 +175,16 @@ AGX_DEV void reset_and_observe(const AgxRobotParams &P, const AgxEnvBuffers &B, 
   }
   ResetDraws<M> D{};
   if (R.u_state) {
-    if (mine) host_reset_draws<M>(P, R, i, D);
+    if (mine) host_reset_draws<M, !ROV>(P, R, i, D);
   } else {
-    wave_reset_draws<M>(R, B.env_index_base + i, ep, mine, D);  // draws are keyed by the GLOBAL env index
+    wave_reset_draws<M, !ROV>(R, B.env_index_base + i, ep, mine, D);  // draws are keyed by the GLOBAL env index
   }
   if (valid) {
-    EnvState s2 = mine ? reset_env<M>(P, B, n, R, i, ep, D) : s;
+    EnvState s2 = mine ? reset_env<M, !ROV>(P, B, n, R, i, ep, D) : s;
     // BaseMultirotor.reset_idx ends with an un-indexed update_states(): every env is refreshed
     // (lean: nobody reads the derived tensors before the next env step rewrites them; the observation reads the body velocities)
     const bool lean = (B.launch_flags & 4) != 0;
-    Derived d2 = lean ? update_states_body(s2) : update_states(s2);
+    Derived d2 = lean ? update_states_body(s2) : (ROV ? update_states_rov(s2) : update_states(s2));
     if (!lean) store_derived(B.derived, n, i, d2);
     if (WITH_OBS) write_obs_position(B, n, i, tgt, obs, s2, d2);
   }
@@ -211,6 +215,33 @@ __global__ void __launch_bounds__(256) k_reset_masked(AgxRobotParams P, AgxEnvBu
   const int flag = B.reset_flag[B.flag_parity];  // (one word: the branch is taken by whole waves)
   const bool any = flag != 0, mine = mask != 0;
   reset_and_observe<M, WITH_OBS>(P, B, n, R, i, valid, any, mine && any, ep, tgt, obs, s, d);
+  if (WITH_OBS) step_rows_signal(B);
+}
+
+// k_reset_masked<8, WITH_OBS> of the ROV kind (AGX_LAUNCH_ROV): the same loads in the same order, reset_and_observe<8, WITH_OBS, true>
+template <bool WITH_OBS>
+__global__ void __launch_bounds__(256) k_reset_masked_rov(AgxRobotParams P, AgxEnvBuffers B, int n, AgxResetArgs R,
+                                                          const float *__restrict__ target, float *__restrict__ obs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) B.reset_flag[B.flag_parity ^ 1] = 0;  // the NEXT step's flag; nobody reads or writes it now
+  if (WITH_OBS) push_wait_for_slot(B);
+  const bool valid = i < n;
+  EnvState s{};
+  Derived d{};
+  V3 tgt{};
+  int mask = 0, ep = 0;
+  if (valid) {
+    s = load_state(B.state, n, i);
+    if (WITH_OBS) {
+      d = load_derived(B.derived, n, i);
+      tgt = V3{AGX_AT(target, 0), AGX_AT(target, 1), AGX_AT(target, 2)};
+    }
+    mask = B.reset_mask[i];
+    if (B.episode_count) ep = B.episode_count[i];
+  }
+  const int flag = B.reset_flag[B.flag_parity];  // (one word: the branch is taken by whole waves)
+  const bool any = flag != 0, mine = mask != 0;
+  reset_and_observe<8, WITH_OBS, true>(P, B, n, R, i, valid, any, mine && any, ep, tgt, obs, s, d);
   if (WITH_OBS) step_rows_signal(B);
 }
 
@@ -387,9 +418,10 @@ __global__ void __launch_bounds__(256) k_reset_assets(AgxEnvBuffers B, int n, in
 static int check_reset(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const AgxResetArgs *R) {
   if (int e = check_common(P, B, n)) return e;
   AGX_REQUIRE(P && R && B->reset_flag && B->reset_mask && B->bounds_min && B->bounds_max, "null argument");
+  const bool rov = (B->launch_flags & AGX_LAUNCH_ROV) != 0;  // no motor draws: u_tau_inc .. u_kT may be NULL
   if (R->u_state) {
-    AGX_REQUIRE(R->u_bounds_lo && R->u_bounds_hi && R->u_tau_inc && R->u_tau_dec && R->u_thrust, "null reset input");
-    AGX_REQUIRE(!P->use_rps || R->u_kT, "null u_kT with use_rps");
+    AGX_REQUIRE(R->u_bounds_lo && R->u_bounds_hi && (rov || (R->u_tau_inc && R->u_tau_dec && R->u_thrust)), "null reset input");
+    AGX_REQUIRE(rov || !P->use_rps || R->u_kT, "null u_kT with use_rps");
     AGX_REQUIRE(!R->randomize_gains || R->u_gains, "null u_gains with randomize_gains");
   } else {
     AGX_REQUIRE(B->episode_count, "device RNG needs buf->episode_count");
@@ -402,6 +434,12 @@ extern "C" int agx_reset_masked(const AgxRobotParams *P, const AgxEnvBuffers *B,
                                 void *stream) {
   if (int e = check_reset(P, B, n, R)) return e;
   const int block = pick_block(n);
+  if (B->launch_flags & AGX_LAUNCH_ROV) {
+    if (int e = check_rov(P, "agx_reset_masked")) return e;
+    hipLaunchKernelGGL((k_reset_masked_rov<false>), dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *P, *B, n, *R,
+                       nullptr, nullptr);
+    return check_launch("agx_reset_masked");
+  }
   AGX_DISPATCH_M(P->num_motors, hipLaunchKernelGGL((k_reset_masked<kM, false>), dim3(blocks_for(n, block)), dim3(block), 0,
                                                    (hipStream_t)stream, *P, *B, n, *R, nullptr, nullptr));
   return check_launch("agx_reset_masked");
@@ -411,6 +449,7 @@ extern "C" int agx_nav_robot_side(const AgxRobotParams *P, const AgxEnvBuffers *
                                   const AgxNavRobotSideArgs *A, void *stream) {
   if (int e = check_reset(P, B, n, R)) return e;
   AGX_REQUIRE(A, "null AgxNavRobotSideArgs");
+  AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_ROV) == 0, "AGX_LAUNCH_ROV: agx_nav_robot_side resets multirotors only (use agx_reset_masked)");
   AGX_REQUIRE(R->u_state == nullptr, "agx_nav_robot_side draws with the device generator only (sync-free mode)");
   AGX_REQUIRE(A->num_sensors >= 0 && (A->num_sensors == 0 || (A->local_pos && A->local_quat && A->sensor_pos && A->sensor_quat)),
               "sensor buffers missing");
@@ -427,6 +466,12 @@ extern "C" int agx_post_step_position(const AgxRobotParams *P, const AgxEnvBuffe
   if (int e = check_reset(P, B, n, R)) return e;
   AGX_REQUIRE(target && obs && B->state && B->derived, "null buffer");
   const int block = pick_block(n);
+  if (B->launch_flags & AGX_LAUNCH_ROV) {  // (never the lane-quad kernel)
+    if (int e = check_rov(P, "agx_post_step_position")) return e;
+    hipLaunchKernelGGL((k_reset_masked_rov<true>), dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *P, *B, n, *R,
+                       target, obs);
+    return check_launch("agx_post_step_position");
+  }
   if (block == 64 && P->num_motors == 4 && option_env_step_quad()) {
     if (R->u_state)
       hipLaunchKernelGGL(k_reset_masked_quad_obs_host_draws, dim3(blocks_for(n, 16)), dim3(64), 0, (hipStream_t)stream, *P, *B, n, *R,

@@ -10,6 +10,12 @@ __global__ void __launch_bounds__(256) k_update_states(AgxEnvBuffers B, int n) {
   EnvState s = load_state(B.state, n, i);
   store_derived(B.derived, n, i, update_states(s));
 }
+__global__ void __launch_bounds__(256) k_update_states_rov(AgxEnvBuffers B, int n) {  // AGX_LAUNCH_ROV
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  EnvState s = load_state(B.state, n, i);
+  store_derived(B.derived, n, i, update_states_rov(s));
+}
 
 // EnvManager.compute_observations (env_manager.py:358-362) on its own: crashes[i] |= the robot's collision sphere at its CURRENT
 // position overlaps an obstacle box -- the predicate of the fused step (sphere_hits_box) without a trajectory.
@@ -48,13 +54,15 @@ __global__ void __launch_bounds__(256) k_controller_wrench(AgxRobotParams P, Agx
 // BaseMultirotor.step(action) of the reference as ONE launch (agx_robot_step; the robot plug-in's super().step()):
 // update_states, clip, controller, allocation + motor model, the per-body force / torque tensors, drag, disturbance.
 // One lane per env, runtime motor count and control law: a plug-in path evaluated between host calls, not a hot loop.
+// ROV: BaseROV.step (base_rov.py:287-298) -- Euler angles without ssa(), per-axis quadratic drag on the linear velocity.
+template <bool ROV>
 __global__ void __launch_bounds__(256) k_robot_step(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ action,
                                                     AgxRobotStepArgs R) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int M = P.num_motors, A = P.num_actions, NB = R.num_bodies;
   EnvState s = load_state(B.state, n, i);
-  const Derived d = update_states(s);
+  const Derived d = ROV ? update_states_rov(s) : update_states(s);
   store_derived(B.derived, n, i, d);
   float a[AGX_MAX_ACTIONS];
 #pragma unroll
@@ -110,10 +118,16 @@ __global__ void __launch_bounds__(256) k_robot_step(AgxRobotParams P, AgxEnvBuff
   // simulate_drag (:260-285), then apply_disturbance (:213-234): both `+=` into body 0
   // (the same drag and disturbance arithmetic as in k_env_step, agx_dyn_env_step.h: written out in both)
   {
-    const float vbn = norm(d.vbody);
-    F[0] += (-P.lin_drag_linear[0] * d.vbody.x) + (-P.lin_drag_quadratic[0] * vbn * d.vbody.x);
-    F[1] += (-P.lin_drag_linear[1] * d.vbody.y) + (-P.lin_drag_quadratic[1] * vbn * d.vbody.y);
-    F[2] += (-P.lin_drag_linear[2] * d.vbody.z) + (-P.lin_drag_quadratic[2] * vbn * d.vbody.z);
+    if (ROV) {  // base_rov.py:260-272: -c_q[k] |v_body[k]| v_body[k], per axis
+      F[0] += (-P.lin_drag_linear[0] * d.vbody.x) + (-P.lin_drag_quadratic[0] * fabsf(d.vbody.x) * d.vbody.x);
+      F[1] += (-P.lin_drag_linear[1] * d.vbody.y) + (-P.lin_drag_quadratic[1] * fabsf(d.vbody.y) * d.vbody.y);
+      F[2] += (-P.lin_drag_linear[2] * d.vbody.z) + (-P.lin_drag_quadratic[2] * fabsf(d.vbody.z) * d.vbody.z);
+    } else {
+      const float vbn = norm(d.vbody);
+      F[0] += (-P.lin_drag_linear[0] * d.vbody.x) + (-P.lin_drag_quadratic[0] * vbn * d.vbody.x);
+      F[1] += (-P.lin_drag_linear[1] * d.vbody.y) + (-P.lin_drag_quadratic[1] * vbn * d.vbody.y);
+      F[2] += (-P.lin_drag_linear[2] * d.vbody.z) + (-P.lin_drag_quadratic[2] * vbn * d.vbody.z);
+    }
     T[0] += (-P.ang_drag_linear[0] * d.wbody.x) + (-P.ang_drag_quadratic[0] * fabsf(d.wbody.x) * d.wbody.x);
     T[1] += (-P.ang_drag_linear[1] * d.wbody.y) + (-P.ang_drag_quadratic[1] * fabsf(d.wbody.y) * d.wbody.y);
     T[2] += (-P.ang_drag_linear[2] * d.wbody.z) + (-P.ang_drag_quadratic[2] * fabsf(d.wbody.z) * d.wbody.z);
@@ -176,7 +190,10 @@ extern "C" int agx_update_states(const AgxEnvBuffers *B, int n, void *stream) {
   if (int e = check_common(nullptr, B, n)) return e;
   AGX_REQUIRE(B->state && B->derived, "null env buffer");
   const int block = pick_block(n);
-  hipLaunchKernelGGL(k_update_states, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n);
+  if (B->launch_flags & AGX_LAUNCH_ROV)
+    hipLaunchKernelGGL(k_update_states_rov, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n);
+  else
+    hipLaunchKernelGGL(k_update_states, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n);
   return check_launch("agx_update_states");
 }
 
@@ -212,7 +229,12 @@ extern "C" int agx_robot_step(const AgxRobotParams *P, const AgxEnvBuffers *B, i
   for (int j = 0; j < (P->root_link_mode ? 1 : P->num_motors); ++j)
     AGX_REQUIRE(R->body_of_motor[j] >= 0 && R->body_of_motor[j] < R->num_bodies, "application mask entry %d = %d outside [0, %d)", j,
                 R->body_of_motor[j], R->num_bodies);
-  hipLaunchKernelGGL(k_robot_step, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *P, *B, n, action, *R);
+  if (B->launch_flags & AGX_LAUNCH_ROV) {
+    if (int e = check_rov(P, "agx_robot_step")) return e;
+    hipLaunchKernelGGL(k_robot_step<true>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *P, *B, n, action, *R);
+  } else {
+    hipLaunchKernelGGL(k_robot_step<false>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *P, *B, n, action, *R);
+  }
   return check_launch("agx_robot_step");
 }
 

@@ -104,6 +104,16 @@ static int check_common(const AgxRobotParams *P, const AgxEnvBuffers *B, int n) 
   return AGX_OK;
 }
 
+// AGX_LAUNCH_ROV (the robot kind BaseROV): the kernels of that kind exist for eight thrusters under the laws that read no Euler
+// angles -- the ROV's are not wrapped to (-pi, pi], which the Lee laws with Euler-angle feedback assume
+static int check_rov(const AgxRobotParams *P, const char *entry) {
+  AGX_REQUIRE(P->num_motors == 8, "%s: AGX_LAUNCH_ROV needs num_motors == 8 (got %d)", entry, P->num_motors);
+  AGX_REQUIRE(P->controller == AGX_CTRL_FULLY_ACTUATED || P->controller == AGX_CTRL_NONE || P->controller == AGX_CTRL_WRENCH,
+              "%s: AGX_LAUNCH_ROV runs the fully actuated law, no_control or an external wrench, not the Lee controller id %d", entry,
+              P->controller);
+  return AGX_OK;
+}
+
 // the lane-quad kernels leave the drag terms out: any non-zero coefficient keeps k_env_step
 static bool has_drag(const AgxRobotParams *P) {
   for (int c = 0; c < 3; ++c)
@@ -149,14 +159,16 @@ struct EnvStepChoice {
   int M, ctrl;        // template arguments of k_env_step_quad_loop<M, CTRL> and k_env_step<M, CTRL, SINGLE, WIDE>
   bool single, wide;  // ... of k_env_step only
   int block, grid;    // threads per workgroup; workgroups that carry envs (the proof-slot launch adds its folding workgroup)
+  bool rov;           // AGX_LAUNCH_ROV: k_env_step_rov<CTRL, SINGLE, WIDE> (one-lane family only: the lane-quad kernels need launch_flags == 0)
 };
 static EnvStepChoice choose_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, int k, const AgxTaskArgs &T) {
   const int block = pick_block(n);
   if (k == 1 && block == 64 && P->num_motors == 4 && P->controller == AGX_CTRL_POSITION && quad_kernel_usable(P, B, &T))
-    return EnvStepChoice{ENV_STEP_QUAD_POSITION, 4, AGX_CTRL_POSITION, true, true, 64, blocks_for(n, 16)};
+    return EnvStepChoice{ENV_STEP_QUAD_POSITION, 4, AGX_CTRL_POSITION, true, true, 64, blocks_for(n, 16), false};
   if (quad_loop_kernel_usable(P, B, n, k))
-    return EnvStepChoice{ENV_STEP_QUAD_LOOP, P->num_motors, P->controller, false, true, 64, blocks_for(n, 16)};
-  return EnvStepChoice{ENV_STEP_ONE_LANE, P->num_motors, P->controller, k == 1, block == 64, block, blocks_for(n, block)};
+    return EnvStepChoice{ENV_STEP_QUAD_LOOP, P->num_motors, P->controller, false, true, 64, blocks_for(n, 16), false};
+  return EnvStepChoice{ENV_STEP_ONE_LANE, P->num_motors, P->controller, k == 1, block == 64, block, blocks_for(n, block),
+                       (B->launch_flags & AGX_LAUNCH_ROV) != 0};
 }
 
 // Dynamic LDS one launch may ask for without saying so first, and the most the 256-thread instance can ask for (obstacles, k = 32).
@@ -179,6 +191,19 @@ static int launch_env_step(const EnvStepChoice &c, size_t lds, hipStream_t strea
   return AGX_OK;
 }
 
+template <int CTRL>
+static int launch_env_step_rov(const EnvStepChoice &c, size_t lds, hipStream_t stream, const AgxRobotParams &P, const AgxEnvBuffers &B, int n,
+                               const float *actions_in, int k, const AgxTaskArgs &T) {
+  const auto kernel = c.single ? (c.wide ? k_env_step_rov<CTRL, true, true> : k_env_step_rov<CTRL, true, false>)
+                               : (c.wide ? k_env_step_rov<CTRL, false, true> : k_env_step_rov<CTRL, false, false>);
+  if (lds > kLdsDefaultMax) {
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEnvStepLdsMax);
+    AGX_REQUIRE(e == hipSuccess, "hipFuncSetAttribute(k_env_step_rov, %zu bytes of LDS): %s", lds, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3(c.grid), dim3(c.block), lds, stream, P, B, n, actions_in, k, T);
+  return AGX_OK;
+}
+
 extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
                             const AgxTaskArgs *task, void *stream) {
   if (int e = check_common(P, B, n)) return e;
@@ -187,7 +212,9 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
   AGX_REQUIRE(k >= 0 && k <= AGX_MAX_SUBSTEPS, "k_substeps out of range: %d", k);
   AGX_REQUIRE(P->controller != AGX_CTRL_WRENCH || k <= 1,
               "external controller (AGX_CTRL_WRENCH): one launch per physics sub-step, the host re-evaluates the controller in between");
-  AGX_REQUIRE((B->launch_flags & ~0xFF0F) == 0, "launch_flags: bits 0-3 and the sub-step index in bits 8-15");
+  AGX_REQUIRE((B->launch_flags & ~(0xFF0F | AGX_LAUNCH_ROV)) == 0, "launch_flags: bits 0-3, the sub-step index in bits 8-15 and AGX_LAUNCH_ROV");
+  if (B->launch_flags & AGX_LAUNCH_ROV)
+    if (int e = check_rov(P, "agx_env_step")) return e;
   AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_BODY_WRENCH) == 0 || P->controller == AGX_CTRL_WRENCH,
               "AGX_LAUNCH_BODY_WRENCH (external robot) goes with AGX_CTRL_WRENCH: actions_in is a wrench [N][6]");
   AGX_REQUIRE((B->launch_flags & 4) == 0 || ((B->launch_flags & 3) == 0 && P->controller != AGX_CTRL_WRENCH &&
@@ -234,6 +261,13 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
     return check_launch("agx_env_step");
   }
   AGX_REQUIRE(lds <= kEnvStepLdsMax, "agx_env_step needs %zu bytes of LDS (> %zu)", lds, kEnvStepLdsMax);
+  if (c.rov) {  // (check_rov above: eight motors, one of these three laws)
+    int e = c.ctrl == AGX_CTRL_FULLY_ACTUATED ? launch_env_step_rov<AGX_CTRL_FULLY_ACTUATED>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)
+            : c.ctrl == AGX_CTRL_NONE         ? launch_env_step_rov<AGX_CTRL_NONE>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)
+                                              : launch_env_step_rov<AGX_CTRL_WRENCH>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T);
+    if (e) return e;
+    return check_launch("agx_env_step");
+  }
   AGX_DISPATCH_M(c.M, AGX_DISPATCH_CTRL(c.ctrl, if (int e = launch_env_step<kM, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)) return e));
   return check_launch("agx_env_step");
 }
@@ -249,6 +283,8 @@ extern "C" int agx_env_step_kernel(const AgxRobotParams *P, const AgxEnvBuffers 
     snprintf(out, (size_t)cap, "k_env_step_quad_position_%d", threads);
   else if (c.family == ENV_STEP_QUAD_LOOP)
     snprintf(out, (size_t)cap, "k_env_step_quad_loop<%d,%d>_%d", c.M, c.ctrl, threads);
+  else if (c.rov)
+    snprintf(out, (size_t)cap, "k_env_step_rov<%d,%s,%s>_%d", c.ctrl, c.single ? "true" : "false", c.wide ? "true" : "false", threads);
   else
     snprintf(out, (size_t)cap, "k_env_step<%d,%d,%s,%s>_%d", c.M, c.ctrl, c.single ? "true" : "false", c.wide ? "true" : "false", threads);
   return AGX_OK;

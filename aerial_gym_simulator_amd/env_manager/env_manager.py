@@ -203,6 +203,9 @@ class EnvManager(BaseManager):
         B.num_boxes = self.scene.num_prims  # collision boxes: one per primitive (= per asset for box scenes)
         imu = self.robot_manager.imu_sensor
         B.body_force = p(imu.body_force) if imu is not None else None
+        # the robot kind (BaseROV: AGX_LAUNCH_ROV), part of launch_flags of EVERY launch of this env manager
+        self._kind_flags = int(getattr(robot, "LAUNCH_FLAGS", 0))
+        B.launch_flags = self._kind_flags
         self._buffers = B
         self._zero_wrench = None
         self._params = robot.params
@@ -220,6 +223,8 @@ class EnvManager(BaseManager):
         M = robot.cfg.control_allocator_config.num_motors
         ctrl = robot.controller
         self._randomize_gains = bool(getattr(ctrl.cfg, "randomize_params", False)) and hasattr(ctrl, "gains_soa")
+        # base_rov.py:171-198 does not call control_allocator.reset_idx: no motor draws, motor state untouched (AGX_LAUNCH_ROV)
+        self._resets_motors = not (self._kind_flags & _lib.LAUNCH_ROV)
         # one flat buffer -> one RNG launch per draw in the sync-free mode
         sizes = dict(bounds_lo=3, bounds_hi=3, state=13, gains=12, tau_inc=M, tau_dec=M, thrust=M, kT=M)
         self._u_flat = torch.zeros(N * sum(sizes.values()), device=dev)
@@ -233,8 +238,11 @@ class EnvManager(BaseManager):
         if self.strict_rng:  # host tensors; otherwise all NULL = device generator
             R.u_bounds_lo, R.u_bounds_hi, R.u_state = p(self._u["bounds_lo"]), p(self._u["bounds_hi"]), p(self._u["state"])
             R.u_gains = p(self._u["gains"]) if self._randomize_gains else None
-            R.u_tau_inc, R.u_tau_dec = p(self._u["tau_inc"]), p(self._u["tau_dec"])
-            R.u_thrust, R.u_kT = p(self._u["thrust"]), p(self._u["kT"])
+            if not self._resets_motors:  # BaseROV.reset_idx draws nothing for the motors: the kernel takes none
+                R.u_tau_inc = R.u_tau_dec = R.u_thrust = R.u_kT = None
+            else:
+                R.u_tau_inc, R.u_tau_dec = p(self._u["tau_inc"]), p(self._u["tau_dec"])
+                R.u_thrust, R.u_kT = p(self._u["thrust"]), p(self._u["kT"])
         R.randomize_gains = int(self._randomize_gains)
         R.seed = self.rng_seed
         for i in range(3):
@@ -367,7 +375,7 @@ class EnvManager(BaseManager):
         maintained ones are one sub-step stale like the reference's (SURVEY appendix A #1); the action history is refused."""
         g = self.global_tensor_dict
         self._lean = True
-        self._buffers.launch_flags = 4
+        self._buffers.launch_flags = 4 | self._kind_flags
         logger.warning("lean step enabled (args={'lean_step': True}, %d envs): robot_euler_angles / robot_vehicle_orientation / "
                        "robot_vehicle_linvel are recomputed from the CURRENT state when read through the dict (tensor references held "
                        "across steps show NaN until then); robot_actions / robot_prev_actions are not maintained." % self.num_envs)
@@ -437,11 +445,12 @@ class EnvManager(BaseManager):
             n = len(env_ids)
             for k in range(4):
                 u["gains"][env_ids, 3 * k:3 * k + 3] = rs.rand(n, 3, tag="gains%d" % k)
-        rs.rand_into(u["tau_inc"], tag="tau_inc")
-        rs.rand_into(u["tau_dec"], tag="tau_dec")
-        rs.rand_into(u["thrust"], tag="thrust")
-        if robot.cfg.control_allocator_config.motor_model_config.use_rps:
-            rs.rand_into(u["kT"], tag="kT")
+        if self._resets_motors:  # (BaseROV: base_rov.py:171-198 ends with the controller's randomize_params)
+            rs.rand_into(u["tau_inc"], tag="tau_inc")
+            rs.rand_into(u["tau_dec"], tag="tau_dec")
+            rs.rand_into(u["thrust"], tag="thrust")
+            if robot.cfg.control_allocator_config.motor_model_config.use_rps:
+                rs.rand_into(u["kT"], tag="kT")
         self.robot_manager.draw_sensor_reset_randoms(env_ids)
 
     def strict_draw_plan(self):
@@ -456,8 +465,8 @@ class EnvManager(BaseManager):
                 or self.scene.num_assets > 0 or sensor is not None or self.robot_manager.imu_sensor is not None
                 or self.robot_manager.robot.cfg.disturbance.enable_disturbance):
             return None
-        names = ["bounds_lo", "bounds_hi", "state", "tau_inc", "tau_dec", "thrust"]
-        if self.robot_manager.robot.cfg.control_allocator_config.motor_model_config.use_rps:
+        names = ["bounds_lo", "bounds_hi", "state"] + (["tau_inc", "tau_dec", "thrust"] if self._resets_motors else [])
+        if self._resets_motors and self.robot_manager.robot.cfg.control_allocator_config.motor_model_config.use_rps:
             names.append("kT")
         bufs = [self._u[k] for k in names]
         index = torch.device(self.device).index
@@ -651,7 +660,7 @@ class EnvManager(BaseManager):
         g, B, robot = self.global_tensor_dict, self._buffers, self.robot_manager.robot
         try:
             for sub in range(max(k, 1)):
-                B.launch_flags = (1 if sub > 0 else 0) | (2 if sub < k - 1 else 0) | (sub << 8)
+                B.launch_flags = (1 if sub > 0 else 0) | (2 if sub < k - 1 else 0) | (sub << 8) | self._kind_flags
                 if k > 0:
                     g["robot_prev_actions"][:] = g["robot_actions"]
                     g["robot_actions"][:] = a
@@ -667,7 +676,7 @@ class EnvManager(BaseManager):
                 _lib.check(self._lib.agx_env_step(self._params, B, self.num_envs, _lib.dptr(w), min(k, 1), self.task_args, self._stream()),
                            "agx_env_step")
         finally:
-            B.launch_flags = 0
+            B.launch_flags = self._kind_flags
 
     # ---- robot plug-in (robots/base_robot.py:10-63, robot_manager.py:486-489) -------------------------------------
     _robot_step_args = None
@@ -748,7 +757,7 @@ class EnvManager(BaseManager):
         self._in_external_simulate = True
         try:
             for sub in range(max(k, 1)):
-                B.launch_flags = (1 if sub > 0 else 0) | (2 if sub < k - 1 else 0) | _lib.LAUNCH_BODY_WRENCH | (sub << 8)
+                B.launch_flags = (1 if sub > 0 else 0) | (2 if sub < k - 1 else 0) | _lib.LAUNCH_BODY_WRENCH | (sub << 8) | self._kind_flags
                 if k > 0:
                     g["robot_prev_actions"][:] = g["robot_actions"]
                     g["robot_actions"][:] = a
@@ -764,7 +773,7 @@ class EnvManager(BaseManager):
                                                   self.task_args, self._stream()), "agx_env_step")
             self._check_unknown_bodies()
         finally:
-            B.launch_flags = 0
+            B.launch_flags = self._kind_flags
             self._robot_substep = 0
             self._in_external_simulate = False
 

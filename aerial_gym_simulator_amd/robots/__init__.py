@@ -3,6 +3,7 @@ from ..config.robot_config import (
     BaseOctarotorCfg,
     BaseOctarotorWithLidar32x512Cfg,
     BaseQuadCfg,
+    BaseROVCfg,
     BaseQuadRootLinkControlCfg,
     BaseQuadWithCamera64x48Cfg,
     BaseQuadWithCameraCfg,
@@ -19,6 +20,7 @@ from ..config.robot_config import (
 )
 from ..registry.robot_registry import robot_registry
 from .base_multirotor import BaseMultirotor
+from .base_rov import BaseROV
 
 robot_registry.register("base_quadrotor", BaseMultirotor, BaseQuadCfg)
 robot_registry.register("base_octarotor", BaseMultirotor, BaseOctarotorCfg)
@@ -36,3 +38,4 @@ robot_registry.register("lmf2_with_camera_64x48", BaseMultirotor, LMF2With64x48C
 robot_registry.register("lmf2_radar", BaseMultirotor, LMF2RadarCfg)  # robots/__init__.py:52 of the reference: the radar task's robot
 robot_registry.register("base_quad_root_link_control", BaseMultirotor, BaseQuadRootLinkControlCfg)
 robot_registry.register("tinyprop", BaseMultirotor, TinyPropCfg)  # robots/__init__.py of the reference: the end-to-end task's airframe
+robot_registry.register("base_rov", BaseROV, BaseROVCfg)  # robots/__init__.py:41 of the reference: the fully actuated ROV (BlueROV airframe)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 17
+#define AGX_ABI_VERSION 18
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -200,10 +200,21 @@ typedef struct AgxEnvBuffers {
                             the NET body-frame wrench on the rigid composite about its centre of mass -- what the robot
                             object's step() left in robot_force_tensor / robot_torque_tensor, reduced by
                             agx_net_body_wrench -- and goes straight to the integrator: no allocation, motor model, drag or
-                            disturbance in this launch (the robot's step() did whatever it does about them).             */
+                            disturbance in this launch (the robot's step() did whatever it does about them).
+                            bit 16 (AGX_LAUNCH_ROV) = the robot is of the kind BaseROV (robots/base_rov.py of the reference): a
+                            rigid body with eight fixed thrusters that differs from the multirotor in three places --
+                            the quadratic drag on the linear velocity is per axis, -c_q[k] |v_body[k]| v_body[k]; the Euler
+                            angles (derived[0..2]) are stored as get_euler_xyz returns them, in [0, 2 pi), not wrapped to
+                            (-pi, pi]; a masked reset leaves motor_thrust, motor_kT, motor_tau_inc and motor_tau_dec of the
+                            resetting envs as they are and consumes no motor draws (AgxResetArgs.u_tau_inc, u_tau_dec,
+                            u_thrust, u_kT may be NULL).  Read by agx_env_step, agx_robot_step, agx_update_states,
+                            agx_reset_masked and agx_post_step_position, which refuse it unless num_motors == 8 and the
+                            controller is AGX_CTRL_FULLY_ACTUATED, AGX_CTRL_NONE or AGX_CTRL_WRENCH (the laws that read no
+                            Euler angles); the other entry points that reset or refresh a robot refuse the flag.      */
 } AgxEnvBuffers;
 #define AGX_LAUNCH_LEAN 4
 #define AGX_LAUNCH_BODY_WRENCH 8
+#define AGX_LAUNCH_ROV 0x10000
 
 const char *agx_last_error(void);
 int agx_abi_version(void);
