@@ -292,7 +292,12 @@ class AgxEndToEndReward(C.Structure):
                 ("diff_gain", C.c_float), ("diff_exp", C.c_float), ("divisor", C.c_float)]
 
 
-ABI_VERSION = 18  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+class AgxComOffset(C.Structure):
+    """the composite's centre of mass in the base-link frame, the trailing argument of agx_env_step_com"""
+    _fields_ = [("c", C.c_float * 3), ("reserved", C.c_float)]
+
+
+ABI_VERSION = 19  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -304,6 +309,8 @@ _SIGNATURES = {
     "agx_copy_f4": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "agx_dynamics_substeps": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, _P]),
     "agx_env_step": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, C.POINTER(AgxTaskArgs), _P]),
+    "agx_env_step_com": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, C.POINTER(AgxTaskArgs),
+                                   C.POINTER(AgxComOffset), _P]),
     "agx_update_states": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P]),
     "agx_collide_spheres_boxes": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P]),
     "agx_controller_wrench": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, _P]),

@@ -524,3 +524,159 @@ class TinyPropCfg:  # tinyprop_config.py:15-166, resources/robots/tinyprop/tinyp
             thrust_to_torque_ratio = 0.01
             use_discrete_approximation = True
             integration_scheme = "rk4"
+
+
+class LMF1Cfg(MagpieCfg):  # lmf1_config.py:15-176, resources/robots/lmf1/model.urdf
+    """lmf2's predecessor: the same airframe layout with a 1.195 kg base link, forces applied at the four prop links, no sensors
+    and no disturbance.  The URDF's fixed joints are kept (5 bodies, ordered by link name: back_left, back_right, front_left,
+    front_right), so allocator column j is body application_mask[j] -- front right, back left, front left, back right.  Its
+    centre of mass is the base-link origin.  Pinned by tests/golden/robot_lmf1.npz (composite of the reference's URDF)."""
+
+    class init_config:
+        min_init_state = [0.0, 0.0, 0.0, -_PI / 6, -_PI / 6, -_PI, 1.0, -0.5, -0.5, -0.5, -0.2, -0.2, -0.2]
+        max_init_state = [1.0, 1.0, 1.0, _PI / 6, _PI / 6, _PI, 1.0, 0.5, 0.5, 0.5, 0.2, 0.2, 0.2]
+
+    class sensor_config:
+        enable_camera = False
+        camera_config = BaseDepthCameraConfig
+        enable_lidar = False
+        lidar_config = BaseLidarConfig
+        enable_imu = False
+        imu_config = BaseImuConfig
+
+    class disturbance:
+        enable_disturbance = False
+        prob_apply_disturbance = 0.0
+        max_force_and_torque_disturbance = [0, 0, 0, 0, 0, 0]
+
+    class robot_asset(_CommonAsset):
+        file = "model.urdf"
+        name = "base_quadrotor"
+        collision_mask = 1
+        angular_damping = 0.02
+        linear_damping = 0.02
+        armature = 0.00001
+        min_state_ratio = [0.1, 0.1, 0.1, 0, 0, -_PI, 1.0, 0, 0, 0, 0, 0, 0]
+        max_state_ratio = [0.9, 0.9, 0.9, 0, 0, _PI, 1.0, 0, 0, 0, 0, 0, 0]
+
+    class robot_model(MagpieCfg.robot_model):  # model.urdf: base 1.195 kg + 4 props of 10 g at (+-0.1, +-0.1, 0)
+        base_mass = 1.195
+        # the URDF collision shape is a 0.5 m cube; the collision model here is a sphere of half its width (DESIGN.md "Collision")
+        collision_sphere_radius = 0.25
+        motor_xyz = [[0.1, -0.1, 0.0], [-0.1, 0.1, 0.0], [0.1, 0.1, 0.0], [-0.1, -0.1, 0.0]]  # in allocator-column order
+
+    class control_allocator_config:
+        num_motors = 4
+        force_application_level = "motor_link"
+        application_mask = [4, 1, 3, 2]  # front right, back left, front left, back right
+        motor_directions = [1, 1, -1, -1]
+        allocation_matrix = [
+            [0.0, 0.0, 0.0, 0.0],
+            [0.0, 0.0, 0.0, 0.0],
+            [1.0, 1.0, 1.0, 1.0],
+            [-0.13, 0.13, 0.13, -0.13],
+            [-0.13, 0.13, -0.13, 0.13],
+            [-0.05, 0.05, -0.05, 0.05],
+        ]
+
+        class motor_model_config:
+            use_rps = True
+            motor_thrust_constant_min = motor_thrust_constant_max = 5.487e-6
+            motor_time_constant_increasing_min = motor_time_constant_increasing_max = 0.025
+            motor_time_constant_decreasing_min = motor_time_constant_decreasing_max = 0.025
+            max_thrust, min_thrust = 20.0, 0.0
+            max_thrust_rate = 100000.0
+            thrust_to_torque_ratio = 0.05
+            use_discrete_approximation = False
+
+
+class BaseRandCfg:  # base_random_config.py:14-227, resources/robots/random/random.urdf
+    """The reference's showcase of an arbitrary configuration: eight motors at arbitrary poses around a base link with a full
+    inertia tensor.  The composite's centre of mass lies at (22.44, 1.75, -2.63) mm from the base-link origin, so this airframe
+    flies through agx_env_step_com (DESIGN.md "integrator").  `allocation_matrix` is the reference's, which it computed about the
+    base-link ORIGIN: the controller is slightly wrong about the airframe it flies, as on the reference.  motor_j is URDF link
+    motor_j and allocator column j; the eight massless arm_motor_j links carry nothing and are left out.  Pinned by
+    tests/golden/robot_base_random.npz (composite of the reference's URDF)."""
+
+    class init_config:
+        min_init_state = [0.0, 0.0, 0.0, 0, 0, -_PI, 1.0, -0.2, -0.2, -0.2, -0.2, -0.2, -0.2]
+        max_init_state = [1.0, 1.0, 1.0, 0, 0, _PI, 1.0, 0.2, 0.2, 0.2, 0.2, 0.2, 0.2]
+
+    class sensor_config:
+        enable_camera = False
+        camera_config = BaseDepthCameraConfig
+        enable_lidar = False
+        lidar_config = BaseLidarConfig
+        enable_imu = False
+        imu_config = BaseImuConfig
+
+    class disturbance:
+        enable_disturbance = True
+        prob_apply_disturbance = 0.05
+        max_force_and_torque_disturbance = [1.5, 1.5, 1.5, 0.25, 0.25, 0.25]
+
+    class damping:
+        linvel_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        linvel_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_linear_damping_coefficient = [0.0, 0.0, 0.0]
+        angular_quadratic_damping_coefficient = [0.0, 0.0, 0.0]
+
+    class robot_asset(_CommonAsset):
+        file = "random.urdf"
+        name = "base_random"
+        angular_damping = 0.0000001
+        linear_damping = 0.0000001
+        min_state_ratio = [0.1, 0.1, 0.1, 0, 0, -_PI, 1.0, -0.5, -0.5, -0.5, -0.2, -0.2, -0.2]
+        max_state_ratio = [0.3, 0.9, 0.9, 0, 0, _PI, 1.0, 0.5, 0.5, 0.5, 0.2, 0.2, 0.2]
+
+    class robot_model:  # random.urdf: base 0.225 kg with a full tensor, eight 3.125 g motor links without inertia of their own
+        base_mass = 0.225
+        base_inertia = [[0.001425189394784859, -0.00026658913320567757, 0.00039128491940189244],
+                        [-0.00026658913320567757, 0.0022903263103270237, -0.00025018840733648744],
+                        [0.00039128491940189244, -0.00025018840733648744, 0.0021842657051118833]]
+        collision_sphere_radius = 0.47291274518274684
+        motor_mass = 0.0031249999999999993
+        motor_xyz = [
+            [0.2824873734152916, -0.0724873734152916, -0.175],
+            [0.21, -0.24499999999999997, -0.27999999999999997],
+            [0.03748737341529165, -0.1424873734152916, 0.034999999999999996],
+            [0.315, 0.13999999999999999, -0.06999999999999999],
+            [0.3524873734152916, 0.28248737341529156, -0.13999999999999999],
+            [0.13999999999999999, 0.13999999999999999, 0.27999999999999997],
+            [0.14248737341529163, 0.0724873734152916, 0.175],
+            [0.315, -0.034999999999999996, -0.034999999999999996],
+        ]
+        motor_rpy = [
+            [-1.5707963267948961, 0.8726646259971647, 1.7272004125383903e-16],
+            [-2.792526803190927, -0.34906585039886595, -3.141592653589793],
+            [0.7853981633974484, -0.6981317007977318, -3.623233072825522e-17],
+            [0.0, -0.34906585039886573, 0.0],
+            [0.1745329251994329, 1.3962634015954642, 0.0],
+            [-1.2217304763960306, 1.5707963267948966, 0.0],
+            [-0.5235987755982989, 1.5707963267948966, 0.0],
+            [0.17453292519943295, -0.8726646259971649, 0.0],
+        ]
+
+    class control_allocator_config:
+        num_motors = 8
+        force_application_level = "motor_link"
+        application_mask = [1 + 8 + i for i in range(8)]
+        motor_directions = [-1, 1, -1, 1, -1, 1, -1, 1]
+        allocation_matrix = [
+            [5.55111512e-17, -3.21393805e-01, -4.54519478e-01, -3.42020143e-01, 9.69846310e-01, 3.42020143e-01, 8.66025404e-01, -7.54406507e-01],
+            [1.00000000e00, -3.42020143e-01, -7.07106781e-01, 0.00000000e00, -1.73648178e-01, 9.39692621e-01, 5.00000000e-01, -1.73648178e-01],
+            [1.66533454e-16, -8.83022222e-01, 5.41675220e-01, 9.39692621e-01, 1.71010072e-01, 1.11022302e-16, 1.11022302e-16, 6.33022222e-01],
+            [1.75000000e-01, 1.23788742e-01, -5.69783368e-02, 1.34977168e-01, 3.36959042e-02, -2.66534135e-01, -7.88397460e-02, -2.06893989e-02],
+            [1.00000000e-02, 2.78845133e-01, -4.32852308e-02, -2.72061766e-01, -1.97793856e-01, 8.63687139e-02, 1.56554446e-01, -1.71261290e-01],
+            [2.82487373e-01, -1.41735490e-01, -8.58541103e-02, 3.84858939e-02, -3.33468026e-01, 8.36741468e-02, 8.46777988e-03, -8.74336259e-02],
+        ]
+
+        class motor_model_config:
+            use_rps = False
+            motor_thrust_constant_min, motor_thrust_constant_max = 0.00000926312, 0.00001826312
+            motor_time_constant_increasing_min, motor_time_constant_increasing_max = 0.01, 0.03
+            motor_time_constant_decreasing_min, motor_time_constant_decreasing_max = 0.005, 0.005
+            max_thrust, min_thrust = 5.0, -5.0
+            max_thrust_rate = 100000.0
+            thrust_to_torque_ratio = 0.01
+            use_discrete_approximation = True

@@ -1,6 +1,6 @@
 #pragma once
 // The one-lane-per-env step kernel k_env_step<M, CTRL, SINGLE, WIDE> (108 instances), its ROV kind k_env_step_rov<CTRL, SINGLE, WIDE>
-// (12 instances) and the occupancy they are compiled for.
+// (12 instances), its off-centre-mass kind k_env_step_com<M, CTRL, SINGLE, WIDE> (72 instances) and the occupancy they are compiled for.
 // Part of the one translation unit agx_dynamics.hip, which alone includes it (after the AGX_DYN_* switches).
 
 namespace agx {
@@ -25,6 +25,8 @@ template <int M, int CTRL, bool SINGLE, bool WIDE>
 __global__ void __launch_bounds__(WIDE ? 64 : 256, WIDE ? 1 : (SINGLE ? env_step_single_waves(M, CTRL) : AGX_DYN_WAVES_LOOP))
     k_env_step(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, int k_arg, AgxTaskArgs T) {
   constexpr bool ROV = false;
+  constexpr bool COM = false;
+  const V3 com{0.0f, 0.0f, 0.0f};
 #include "agx_dyn_env_step_body.h"
 }
 
@@ -36,6 +38,21 @@ __global__ void __launch_bounds__(WIDE ? 64 : 256, WIDE ? 1 : (SINGLE ? env_step
   static_assert(CTRL == AGX_CTRL_FULLY_ACTUATED || CTRL == AGX_CTRL_NONE || CTRL == AGX_CTRL_WRENCH, "the laws that read no Euler angles");
   constexpr int M = 8;
   constexpr bool ROV = true;
+  constexpr bool COM = false;
+  const V3 com{0.0f, 0.0f, 0.0f};
+#include "agx_dyn_env_step_body.h"
+}
+
+// The kind of a multirotor whose centre of mass is not the base-link origin (agx_env_step_com): four or eight motors under every law
+// k_env_step is compiled for (72 instances), at the occupancy of the k_env_step instance of the same arguments.  The offset travels
+// as a trailing kernel argument: AgxRobotParams, AgxEnvBuffers and AgxTaskArgs stay what the other kernels receive.
+template <int M, int CTRL, bool SINGLE, bool WIDE>
+__global__ void __launch_bounds__(WIDE ? 64 : 256, WIDE ? 1 : (SINGLE ? env_step_single_waves(M, CTRL) : AGX_DYN_WAVES_LOOP))
+    k_env_step_com(AgxRobotParams P, AgxEnvBuffers B, int n, const float *__restrict__ actions_in, int k_arg, AgxTaskArgs T, AgxComOffset C) {
+  static_assert(M == 4 || M == 8, "compiled for four and eight motors");
+  constexpr bool ROV = false;
+  constexpr bool COM = true;
+  const V3 com{C.c[0], C.c[1], C.c[2]};
 #include "agx_dyn_env_step_body.h"
 }
 }  // namespace agx

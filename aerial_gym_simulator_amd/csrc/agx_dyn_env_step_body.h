@@ -1,9 +1,11 @@
-// The body of the one-lane env-step kernels, included INSIDE k_env_step<M, CTRL, SINGLE, WIDE> and k_env_step_rov<CTRL, SINGLE, WIDE>
-// (agx_dyn_env_step.h, nowhere else; no include guard on purpose).  The including kernel provides the kernel parameters P, B, n,
-// actions_in, k_arg, T and the compile-time constants M, CTRL, SINGLE, WIDE and ROV.  ROV: the robot kind BaseROV of the reference
-// (AGX_LAUNCH_ROV) -- per-axis quadratic drag on the linear velocity, Euler angles stored without ssa().  Written as text both
-// kernels share rather than as a device function both call: the multirotor instances then compile from the statements they were
-// compiled from before the ROV kind existed, to the same instructions.
+// The body of the one-lane env-step kernels, included INSIDE k_env_step<M, CTRL, SINGLE, WIDE>, k_env_step_rov<CTRL, SINGLE, WIDE> and
+// k_env_step_com<M, CTRL, SINGLE, WIDE> (agx_dyn_env_step.h, nowhere else; no include guard on purpose).  The including kernel provides
+// the kernel parameters P, B, n, actions_in, k_arg, T and the compile-time constants M, CTRL, SINGLE, WIDE, ROV and COM, and the
+// vector `com`.  ROV: the robot kind BaseROV of the reference (AGX_LAUNCH_ROV) -- per-axis quadratic drag on the linear velocity,
+// Euler angles stored without ssa().  COM: the composite's centre of mass lies at `com` in the base-link frame, not at its origin
+// (agx_env_step_com) -- the root body's force gets its lever arm, the base-link position follows the turning body.  Written as text
+// the kernels share rather than as a device function they call: the multirotor instances then compile from the statements they
+// were compiled from before the other kinds existed, to the same instructions.
   const int k = SINGLE ? 1 : k_arg;
   extern __shared__ float traj[];  // [k][3][blockDim] sub-step positions (only with obstacles)
   const int tid = threadIdx.x, bd = blockDim.x;
@@ -148,10 +150,20 @@
 #pragma unroll
         for (int c = 0; c < 6; ++c) bw[c] = split_root ? bw[c] + (dr[c] + di[c]) : (bw[c] + dr[c]) + di[c];
       }
+      if (COM && !body_wrench) {
+        // the root body's entry acts at the base-link origin: the allocator's wrench in root-link mode (then bw IS that entry),
+        // else drag + disturbance (0 `+=` the one, `+=` the other: an absent term is +0).  A body wrench handed in
+        // (AGX_LAUNCH_BODY_WRENCH) is about the centre of mass already (agx_net_body_wrench).
+        const V3 f_root = root_link ? V3{bw[0], bw[1], bw[2]} : V3{dr[0] + di[0], dr[1] + di[1], dr[2] + di[2]};
+        const V3 lever = com_root_torque(f_root, com);
+        bw[3] = bw[3] + lever.x; bw[4] = bw[4] + lever.y; bw[5] = bw[5] + lever.z;
+      }
       if (B.body_force && sub == k - 1) {  // what the IMU's force sensor sees (agx_imu_update)
         AGX_AT(B.body_force, 0) = bw[0]; AGX_AT(B.body_force, 1) = bw[1]; AGX_AT(B.body_force, 2) = bw[2];
       }
+      const Q4 q_before = s.q;
       integrate(P, s, V3{bw[0], bw[1], bw[2]}, V3{bw[3], bw[4], bw[5]});
+      if (COM) s.p = com_position_correction(s.p, q_before, s.q, com);
       if (B.boxes) {
         traj[(sub * 3 + 0) * bd + tid] = s.p.x;
         traj[(sub * 3 + 1) * bd + tid] = s.p.y;

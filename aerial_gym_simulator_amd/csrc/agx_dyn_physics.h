@@ -273,6 +273,19 @@ AGX_DEV void integrate(const AgxRobotParams &P, EnvState &s, V3 Fb, V3 Tb) {
   s.w = w_new;
 }
 
+// ---- centre of mass off the base-link origin (k_env_step_com; DESIGN.md "integrator") ----
+// The state keeps the reference's meaning: p, q the base-link frame, v the velocity of the mass centre, w the angular velocity.
+// c: the composite's centre of mass in the base-link frame.
+// The root body's entry of robot_force_tensor acts at the base-link origin, -c from the mass centre: about the mass centre its
+// force F_root adds the torque (-c) x F_root = F_root x c.
+AGX_DEV V3 com_root_torque(V3 F_root, V3 c) { return cross(F_root, c); }
+// integrate() has moved the mass centre by v_new dt and turned the body about it from q0 to q1, and left p + v_new dt in p: the
+// base-link origin is where the mass centre is minus R(q1) c, i.e. p + (R(q0) c - R(q1) c), component by component.
+AGX_DEV V3 com_position_correction(V3 p, Q4 q0, Q4 q1, V3 c) {
+  V3 a = quat_rotate(q0, c), b = quat_rotate(q1, c);
+  return V3{p.x + (a.x - b.x), p.y + (a.y - b.y), p.z + (a.z - b.z)};
+}
+
 #pragma clang fp contract(off)  // everything below: one IEEE operation per + - * /
 
 // sphere (robot collision sphere, quad.urdf:16) vs obstacle OBBs; replaces the PhysX

@@ -161,8 +161,10 @@ struct EnvStepChoice {
   int block, grid;    // threads per workgroup; workgroups that carry envs (the proof-slot launch adds its folding workgroup)
   bool rov;           // AGX_LAUNCH_ROV: k_env_step_rov<CTRL, SINGLE, WIDE> (one-lane family only: the lane-quad kernels need launch_flags == 0)
 };
-static EnvStepChoice choose_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, int k, const AgxTaskArgs &T) {
+// com: agx_env_step_com -- k_env_step_com<M, CTRL, SINGLE, WIDE>, of the one-lane family at every batch size (the lane-quad kernels do not carry the offset)
+static EnvStepChoice choose_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, int k, const AgxTaskArgs &T, bool com = false) {
   const int block = pick_block(n);
+  if (com) return EnvStepChoice{ENV_STEP_ONE_LANE, P->num_motors, P->controller, k == 1, block == 64, block, blocks_for(n, block), false};
   if (k == 1 && block == 64 && P->num_motors == 4 && P->controller == AGX_CTRL_POSITION && quad_kernel_usable(P, B, &T))
     return EnvStepChoice{ENV_STEP_QUAD_POSITION, 4, AGX_CTRL_POSITION, true, true, 64, blocks_for(n, 16), false};
   if (quad_loop_kernel_usable(P, B, n, k))
@@ -204,10 +206,36 @@ static int launch_env_step_rov(const EnvStepChoice &c, size_t lds, hipStream_t s
   return AGX_OK;
 }
 
-extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
-                            const AgxTaskArgs *task, void *stream) {
+template <int M, int CTRL>
+static int launch_env_step_com(const EnvStepChoice &c, size_t lds, hipStream_t stream, const AgxRobotParams &P, const AgxEnvBuffers &B, int n,
+                               const float *actions_in, int k, const AgxTaskArgs &T, const AgxComOffset &com) {
+  const auto kernel = c.single ? (c.wide ? k_env_step_com<M, CTRL, true, true> : k_env_step_com<M, CTRL, true, false>)
+                               : (c.wide ? k_env_step_com<M, CTRL, false, true> : k_env_step_com<M, CTRL, false, false>);
+  if (lds > kLdsDefaultMax) {
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEnvStepLdsMax);
+    AGX_REQUIRE(e == hipSuccess, "hipFuncSetAttribute(k_env_step_com, %zu bytes of LDS): %s", lds, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3(c.grid), dim3(c.block), lds, stream, P, B, n, actions_in, k, T, com);
+  return AGX_OK;
+}
+
+// agx_env_step_com: the kernels of that kind exist for four and eight motors and write no IMU force
+static int check_com(const AgxRobotParams *P, const AgxEnvBuffers *B) {
+  AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_ROV) == 0, "agx_env_step_com: AGX_LAUNCH_ROV -- the ROV kind carries no centre-of-mass offset");
+  AGX_REQUIRE(P->num_motors == 4 || P->num_motors == 8, "agx_env_step_com needs num_motors == 4 or 8 (got %d)", P->num_motors);
+  AGX_REQUIRE(B->body_force == nullptr,
+              "agx_env_step_com: buf->body_force is set -- an IMU on an airframe with an off-centre mass is not modelled (no lever-arm terms)");
+  AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_LEAN) == 0, "agx_env_step_com: AGX_LAUNCH_LEAN is not available with a centre-of-mass offset");
+  return AGX_OK;
+}
+
+// agx_env_step and agx_env_step_com (com != NULL): the same checks, the same launch geometry
+static int env_step(const char *entry, const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
+                    const AgxTaskArgs *task, const AgxComOffset *com, void *stream) {
   if (int e = check_common(P, B, n)) return e;
   AGX_REQUIRE(P != nullptr, "null params");
+  if (com)
+    if (int e = check_com(P, B)) return e;
   AGX_REQUIRE(actions_in != nullptr, "null actions");
   AGX_REQUIRE(k >= 0 && k <= AGX_MAX_SUBSTEPS, "k_substeps out of range: %d", k);
   AGX_REQUIRE(P->controller != AGX_CTRL_WRENCH || k <= 1,
@@ -233,7 +261,7 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
     AGX_REQUIRE((!T.successes && !T.timeouts && !T.counters) || (T.successes && T.timeouts && T.counters && T.kind == AGX_TASK_NAVIGATION),
                 "navigation bookkeeping in the epilogue needs successes, timeouts and counters, and the navigation task kind");
   }
-  const EnvStepChoice c = choose_env_step(P, B, n, k, T);
+  const EnvStepChoice c = choose_env_step(P, B, n, k, T, com != nullptr);
   const dim3 grid(c.grid), block(c.block);
   if (c.family == ENV_STEP_QUAD_POSITION) {
     // (with proof slots: one more workgroup, the first, folds the previous launch's slots into the host record)
@@ -268,8 +296,27 @@ extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int
     if (e) return e;
     return check_launch("agx_env_step");
   }
+  if (com) {  // (check_com above: four or eight motors)
+    if (c.M == 4) {
+      AGX_DISPATCH_CTRL(c.ctrl, if (int e = launch_env_step_com<4, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T, *com)) return e);
+    } else {
+      AGX_DISPATCH_CTRL(c.ctrl, if (int e = launch_env_step_com<8, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T, *com)) return e);
+    }
+    return check_launch(entry);
+  }
   AGX_DISPATCH_M(c.M, AGX_DISPATCH_CTRL(c.ctrl, if (int e = launch_env_step<kM, kC>(c, lds, (hipStream_t)stream, *P, *B, n, actions_in, k, T)) return e));
   return check_launch("agx_env_step");
+}
+
+extern "C" int agx_env_step(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
+                            const AgxTaskArgs *task, void *stream) {
+  return env_step("agx_env_step", P, B, n, actions_in, k, task, nullptr, stream);
+}
+
+extern "C" int agx_env_step_com(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, const float *actions_in, int k,
+                                const AgxTaskArgs *task, const AgxComOffset *com, void *stream) {
+  AGX_REQUIRE(com != nullptr, "agx_env_step_com: null centre-of-mass offset");
+  return env_step("agx_env_step_com", P, B, n, actions_in, k, task, com, stream);
 }
 
 extern "C" int agx_env_step_kernel(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, int k, const AgxTaskArgs *task, char *out,

@@ -209,6 +209,12 @@ class EnvManager(BaseManager):
         self._buffers = B
         self._zero_wrench = None
         self._params = robot.params
+        # centre of mass off the base-link origin (robot.com_offset: base_random, an asymmetric payload): the three env-step call
+        # sites go through agx_env_step_com; None: agx_env_step
+        self._com = getattr(robot, "com_offset", None)
+        if self._com is not None and self.env_args.get("lean_step"):
+            raise ValueError("args={'lean_step': True} with a robot whose centre of mass is off the base-link origin: "
+                             "agx_env_step_com has no lean stores")
         robot._env_binding = self
         robot.controller._env_binding = self
         self._make_reset_args()
@@ -639,16 +645,30 @@ class EnvManager(BaseManager):
             self._simulate_with_external_robot(a, num_substeps)
         elif getattr(self.robot_manager.robot, "external_controller", False):
             self._simulate_with_external_controller(a, num_substeps)
-        else:
+        elif self._com is None:
             _lib.check(
                 self._lib.agx_env_step(self._params, self._buffers, self.num_envs, _lib.dptr(a), num_substeps, self.task_args,
                                        self._stream()),
                 "agx_env_step",
             )
+        else:
+            self._env_step(self._params, a, num_substeps)
         self._produced.difference_update((self.REWARD, self.RESET_SET, self.OBSERVATION))  # (simulate() by hand: of the state before)
         if self.task_args is not None:  # the fused epilogue wrote the reward, the flags and this step's reset set
             self._produced.update((self.REWARD, self.RESET_SET))
         self.robot_manager.post_physics_step(num_substeps)
+
+    _com = None
+
+    def _env_step(self, params, actions_in, k):
+        """the env-step launch of the three paths (fused step, external controller, external robot): agx_env_step, or
+        agx_env_step_com for a robot whose centre of mass is off the base-link origin"""
+        if self._com is None:
+            _lib.check(self._lib.agx_env_step(params, self._buffers, self.num_envs, _lib.dptr(actions_in), k, self.task_args, self._stream()),
+                       "agx_env_step")
+        else:
+            _lib.check(self._lib.agx_env_step_com(params, self._buffers, self.num_envs, _lib.dptr(actions_in), k, self.task_args, self._com,
+                                                  self._stream()), "agx_env_step_com")
 
     def _simulate_with_external_controller(self, a, k):
         """A controller class the user registered (torch code, controller_registry.register_controller): per physics
@@ -673,8 +693,7 @@ class EnvManager(BaseManager):
                     if self._zero_wrench is None:
                         self._zero_wrench = torch.zeros(self.num_envs, 6, dtype=torch.float32, device=a.device)
                     w = self._zero_wrench
-                _lib.check(self._lib.agx_env_step(self._params, B, self.num_envs, _lib.dptr(w), min(k, 1), self.task_args, self._stream()),
-                           "agx_env_step")
+                self._env_step(self._params, w, min(k, 1))
         finally:
             B.launch_flags = self._kind_flags
 
@@ -769,8 +788,7 @@ class EnvManager(BaseManager):
                                                              _lib.dptr(self._net_wrench), self._stream()), "agx_net_body_wrench")
                 else:
                     self._net_wrench.zero_()
-                _lib.check(self._lib.agx_env_step(P_wrench, B, self.num_envs, _lib.dptr(self._net_wrench), min(k, 1),
-                                                  self.task_args, self._stream()), "agx_env_step")
+                self._env_step(P_wrench, self._net_wrench, min(k, 1))
             self._check_unknown_bodies()
         finally:
             B.launch_flags = self._kind_flags

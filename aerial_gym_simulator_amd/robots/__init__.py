@@ -3,6 +3,7 @@ from ..config.robot_config import (
     BaseOctarotorCfg,
     BaseOctarotorWithLidar32x512Cfg,
     BaseQuadCfg,
+    BaseRandCfg,
     BaseROVCfg,
     BaseQuadRootLinkControlCfg,
     BaseQuadWithCamera64x48Cfg,
@@ -12,6 +13,7 @@ from ..config.robot_config import (
     BaseQuadWithFaceIDNormalCameraCfg,
     BaseQuadWithLidarCfg,
     BaseQuadWithStereoCameraCfg,
+    LMF1Cfg,
     LMF2Cfg,
     LMF2RadarCfg,
     LMF2With64x48CameraCfg,
@@ -39,3 +41,5 @@ robot_registry.register("lmf2_radar", BaseMultirotor, LMF2RadarCfg)  # robots/__
 robot_registry.register("base_quad_root_link_control", BaseMultirotor, BaseQuadRootLinkControlCfg)
 robot_registry.register("tinyprop", BaseMultirotor, TinyPropCfg)  # robots/__init__.py of the reference: the end-to-end task's airframe
 robot_registry.register("base_rov", BaseROV, BaseROVCfg)  # robots/__init__.py:41 of the reference: the fully actuated ROV (BlueROV airframe)
+robot_registry.register("base_random", BaseMultirotor, BaseRandCfg)  # robots/__init__.py:40 of the reference: eight motors at arbitrary poses, centre of mass off the base link
+robot_registry.register("lmf1", BaseMultirotor, LMF1Cfg)  # robots/__init__.py:50 of the reference

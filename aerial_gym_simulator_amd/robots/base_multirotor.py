@@ -11,7 +11,7 @@ from ..control.control_allocation import ControlAllocator
 from ..tensors import aos_view, soa
 from ..utils.logging import CustomLogger
 from .base_robot import BaseRobot
-from .robot_model import pack_robot_params, robot_params_dict
+from .robot_model import pack_com_offset, pack_robot_params, robot_params_dict
 
 logger = CustomLogger("base_multirotor")
 
@@ -68,6 +68,13 @@ class BaseMultirotor(BaseRobot):
             kind = "wrench"
         self.params_dict = robot_params_dict(self.cfg, self.controller_config, kind, g["sim_config"])
         self.params = pack_robot_params(self.params_dict)
+        # A composite whose centre of mass is not the base-link origin (base_random; an asymmetric payload): EnvManager steps it
+        # through agx_env_step_com with this offset.  None: the ordinary agx_env_step.
+        self.com_offset = pack_com_offset(self.params_dict)
+        if self.com_offset is not None and bool(getattr(self.cfg.sensor_config, "enable_imu", False)):
+            raise ValueError(
+                f"robot '{self.cfg.robot_asset.name}': enable_imu with a centre of mass at {self.params_dict['com']} m from the base-link "
+                "origin -- the IMU's lever-arm terms (an accelerometer away from the mass centre) are not modelled")
         # A robot CLASS (robot_registry.register) that overrides step(): the reference's plug-in contract (base_robot.py:10-63).
         # It is called by the host once per physics sub-step; what it leaves in the per-body tensors is integrated.
         self.external_robot = type(self).step is not BaseMultirotor.step

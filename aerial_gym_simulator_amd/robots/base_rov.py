@@ -37,6 +37,9 @@ class BaseROV(BaseMultirotor):
                 f"BaseROV with controller '{self.controller_name}' ({self.params_dict['num_motors']} motors): the ROV kernels are built "
                 "for eight thrusters under the fully actuated law, no_control or an external controller class -- its Euler angles "
                 "are not wrapped to (-pi, pi], which the Lee controllers with Euler-angle feedback assume")
+        if self.com_offset is not None:
+            raise ValueError(f"BaseROV with a centre of mass at {self.params_dict['com']} m from the base-link origin: the ROV kernels "
+                             "(AGX_LAUNCH_ROV) carry no centre-of-mass offset")
         d = self.cfg.damping
         self.body_vel_linear_damping_coefficient = torch.tensor(d.linvel_linear_damping_coefficient, device=dev)
         self.body_vel_quadratic_damping_coefficient = torch.tensor(d.linvel_quadratic_damping_coefficient, device=dev)

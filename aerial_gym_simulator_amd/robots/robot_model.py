@@ -145,8 +145,9 @@ def robot_params_dict(robot_cfg, controller_cfg, controller_kind, sim_cfg):
     mm = ca.motor_model_config
     model = robot_cfg.robot_model
     mass, com, inertia = composite_body(model)
-    if np.abs(com).max() > 1e-9:
-        raise NotImplementedError("robots whose COM is not at the base-link origin are not supported yet")
+    # the composite's centre of mass in the base-link frame, float64 rounded to fp32 once; below 1e-9 m it is the origin (the
+    # symmetric airframes' rounding residue).  Off the origin the env step goes through agx_env_step_com (EnvManager).
+    com32 = com.astype(np.float32) if np.abs(com).max() > 1e-9 else np.zeros(3, np.float32)
     M = int(ca.num_motors)
     A = np.asarray(ca.allocation_matrix, dtype=np.float32)
     if A.shape != (6, M):
@@ -187,7 +188,21 @@ def robot_params_dict(robot_cfg, controller_cfg, controller_kind, sim_cfg):
         max_linear_velocity=float(robot_cfg.robot_asset.max_linear_velocity),
         max_angular_velocity=float(robot_cfg.robot_asset.max_angular_velocity),
         collision_radius=float(model.collision_sphere_radius),
+        com=[float(x) for x in com32],
     )
+
+
+def pack_com_offset(d):
+    """dict (robot_params_dict) -> the AgxComOffset of agx_env_step_com, or None for a robot whose centre of mass is the base-link
+    origin (the ordinary agx_env_step)"""
+    from .._lib import AgxComOffset
+
+    com = np.asarray(d.get("com", [0.0, 0.0, 0.0]), dtype=np.float32)
+    if not com.any():
+        return None
+    C = AgxComOffset()
+    _fill(C.c, com)
+    return C
 
 
 def pack_robot_params(d):

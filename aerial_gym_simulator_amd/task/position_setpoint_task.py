@@ -80,6 +80,7 @@ class PositionSetpointTask(BaseTask):
                   and not getattr(env.robot_manager.robot, "external_controller", False)
                   and not getattr(env.robot_manager.robot, "external_robot", False)
                   and not env.robot_manager.robot.cfg.disturbance.enable_disturbance
+                  and env._com is None  # centre of mass off the base link: agx_env_step_com, which the step plans do not launch
                   and e.num_physics_steps_per_env_step_std == 0 and not self.task_config.return_state_before_reset)
         draws = env.strict_draw_plan() if (plain and env.strict_rng) else None
         if plain and (not env.strict_rng or draws is not None):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 18
+#define AGX_ABI_VERSION 19
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -289,6 +289,27 @@ int agx_env_step(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num
  * list it (bench.py pairs its live launch time with the committed rocprofv3 counters of that instance).             */
 int agx_env_step_kernel(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs, int k_substeps,
                         const AgxTaskArgs *task, char *out, int out_capacity);
+
+/* agx_env_step for a multirotor whose centre of mass is NOT the base-link origin (an asymmetric payload; the reference's
+ * base_random).  com->c: the composite's centre of mass in the base-link frame [m].  The state tensor keeps the reference's
+ * meaning (the PhysX tensor convention): position and attitude are the base-link frame's, the linear velocity is the velocity
+ * of the mass centre, the angular velocity the body's.  Against agx_env_step two things change, per physics sub-step:
+ *   - the root body's entry of robot_force_tensor -- the allocator's wrench in root-link mode, plus drag, plus disturbance --
+ *     acts at the base-link origin: its force F_root adds the torque cross(F_root, c) about the mass centre.  (The motor
+ *     links' arms are in params->wrench_map, which is about the mass centre; a net body wrench handed in under
+ *     AGX_LAUNCH_BODY_WRENCH is about the mass centre already, agx_net_body_wrench with pos = xyz - com.)
+ *   - the integrator moves the mass centre and turns the body about it: behind its p' = p + v dt,
+ *     p'' = p' + (quat_rotate(q, c) - quat_rotate(q', c)) with q, q' the attitude before and after the update.
+ * Everything that reads the state -- controllers, rewards, observations, the collision sphere (centred at p), sensor poses --
+ * reads it as before.  c = 0 is the ordinary dynamics.  Runs the one-lane kernels k_env_step_com<M, CTRL, SINGLE, WIDE> at every
+ * batch size, for 4 and 8 motors under every controller id.  Refused (AGX_E_ARG): AGX_LAUNCH_ROV, AGX_LAUNCH_LEAN, another
+ * motor count, a non-NULL buf->body_force (the IMU's lever-arm terms are not modelled).                                     */
+typedef struct AgxComOffset {
+  float c[3];
+  float reserved;
+} AgxComOffset;
+int agx_env_step_com(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs, const float *actions_in, int k_substeps,
+                     const AgxTaskArgs *task, const AgxComOffset *com, void *stream);
 
 /* EnvManager.compute_observations alone (env_manager.py:358-362; SURVEY 8b's minimum export set): crashes[i] |= the robot's
  * collision sphere (params->collision_radius) at its CURRENT position overlaps one of the env's obstacle boxes (buf->boxes,
