@@ -10,14 +10,6 @@
 
 namespace agx {
 
-#define E2E_AT(p, c) (p)[(size_t)(c) * (size_t)n + (size_t)i]
-
-// gain * exp(-e * x * x) and gain * (exp(-e * x * x) - 1): exp_func / exp_penalty_func (:255-264)
-AGX_DEV float e2e_exp(float x, float gain, float e) { return gain * exp_cw((-e * x) * x); }
-AGX_DEV float e2e_exp_penalty(float x, float gain, float e) { return gain * (exp_cw((-e * x) * x) - 1.0f); }
-// torch.sum(x, dim=1) of three / four columns, left to right
-AGX_DEV float e2e_sum3(float a, float b, float c) { return (a + b) + c; }
-AGX_DEV float e2e_sum4(float a, float b, float c, float d) { return ((a + b) + c) + d; }
 // torch.clamp(x, -1, 1): a NaN stays a NaN
 AGX_DEV float e2e_clamp1(float x) { return x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x); }
 
@@ -34,34 +26,34 @@ __global__ void __launch_bounds__(256) k_e2e_pre_step(AgxEnvBuffers B, int n, co
   o.z = (e2e_clamp1(a.z) * (L.max[2] - L.min[2])) / 2.0f + (L.max[2] + L.min[2]) / 2.0f;
   o.w = (e2e_clamp1(a.w) * (L.max[3] - L.min[3])) / 2.0f + (L.max[3] + L.min[3]) / 2.0f;
   *reinterpret_cast<float4 *>(actions + (size_t)i * 4) = o;
-  E2E_AT(prev_position, 0) = E2E_AT(B.state, 0);
-  E2E_AT(prev_position, 1) = E2E_AT(B.state, 1);
-  E2E_AT(prev_position, 2) = E2E_AT(B.state, 2);
+  AGX_TASK_AT(prev_position, 0) = AGX_TASK_AT(B.state, 0);
+  AGX_TASK_AT(prev_position, 1) = AGX_TASK_AT(B.state, 1);
+  AGX_TASK_AT(prev_position, 2) = AGX_TASK_AT(B.state, 2);
 }
 
 // compute_reward (:267-309), before the crash line
 AGX_DEV float e2e_reward_value(const AgxEndToEndReward &K, V3 err, float dist, float prev_dist, Q4 q, V3 v, V3 w, float4 a, float4 pa) {
   const float ez = err.z * K.z_error_weight;  // pos_error[:, 2] *= 11 AFTER the two distances were taken (:278-282)
-  const float pos_reward = e2e_sum3(e2e_exp(err.x, K.pos_gain[0], K.pos_exp[0]), e2e_exp(err.y, K.pos_gain[0], K.pos_exp[0]),
-                                    e2e_exp(ez, K.pos_gain[0], K.pos_exp[0])) +
-                           e2e_sum3(e2e_exp(err.x, K.pos_gain[1], K.pos_exp[1]), e2e_exp(err.y, K.pos_gain[1], K.pos_exp[1]),
-                                    e2e_exp(ez, K.pos_gain[1], K.pos_exp[1]));
+  const float pos_reward = sum3(gain_exp(err.x, K.pos_gain[0], K.pos_exp[0]), gain_exp(err.y, K.pos_gain[0], K.pos_exp[0]),
+                                gain_exp(ez, K.pos_gain[0], K.pos_exp[0])) +
+                           sum3(gain_exp(err.x, K.pos_gain[1], K.pos_exp[1]), gain_exp(err.y, K.pos_gain[1], K.pos_exp[1]),
+                                gain_exp(ez, K.pos_gain[1], K.pos_exp[1]));
   const V3 ups = quat_rotate(q, V3{0.0f, 0.0f, 1.0f});   // quat_axis(q, 2)
-  const float upright_reward = e2e_exp(1.0f - ups.z, K.upright_gain, K.upright_exp);
+  const float upright_reward = gain_exp(1.0f - ups.z, K.upright_gain, K.upright_exp);
   const V3 forw = quat_rotate(q, V3{1.0f, 0.0f, 0.0f});  // quat_axis(q, 0)
-  const float alignment_reward = e2e_exp(1.0f - forw.x, K.alignment_gain, K.alignment_exp);
-  const float angvel_reward = e2e_sum3(e2e_exp(w.x, K.angvel_gain, K.angvel_exp), e2e_exp(w.y, K.angvel_gain, K.angvel_exp),
-                                       e2e_exp(w.z, K.angvel_gain, K.angvel_exp));
-  const float vel_reward = e2e_sum3(e2e_exp(v.x, K.vel_gain, K.vel_exp), e2e_exp(v.y, K.vel_gain, K.vel_exp),
-                                    e2e_exp(v.z, K.vel_gain, K.vel_exp));
-  const float action_cost = e2e_sum4(e2e_exp_penalty(a.x - K.hover_thrust, K.action_gain, K.action_exp),
-                                     e2e_exp_penalty(a.y - K.hover_thrust, K.action_gain, K.action_exp),
-                                     e2e_exp_penalty(a.z - K.hover_thrust, K.action_gain, K.action_exp),
-                                     e2e_exp_penalty(a.w - K.hover_thrust, K.action_gain, K.action_exp));
+  const float alignment_reward = gain_exp(1.0f - forw.x, K.alignment_gain, K.alignment_exp);
+  const float angvel_reward = sum3(gain_exp(w.x, K.angvel_gain, K.angvel_exp), gain_exp(w.y, K.angvel_gain, K.angvel_exp),
+                                   gain_exp(w.z, K.angvel_gain, K.angvel_exp));
+  const float vel_reward = sum3(gain_exp(v.x, K.vel_gain, K.vel_exp), gain_exp(v.y, K.vel_gain, K.vel_exp),
+                                gain_exp(v.z, K.vel_gain, K.vel_exp));
+  const float action_cost = sum4(gain_exp_penalty(a.x - K.hover_thrust, K.action_gain, K.action_exp),
+                                 gain_exp_penalty(a.y - K.hover_thrust, K.action_gain, K.action_exp),
+                                 gain_exp_penalty(a.z - K.hover_thrust, K.action_gain, K.action_exp),
+                                 gain_exp_penalty(a.w - K.hover_thrust, K.action_gain, K.action_exp));
   const float closer = prev_dist - dist;
   const float towards_goal_reward = (closer >= 0.0f) ? K.closer_gain * closer : K.farther_gain * closer;
-  const float diff_penalty = e2e_sum4(e2e_exp_penalty(a.x - pa.x, K.diff_gain, K.diff_exp), e2e_exp_penalty(a.y - pa.y, K.diff_gain, K.diff_exp),
-                                      e2e_exp_penalty(a.z - pa.z, K.diff_gain, K.diff_exp), e2e_exp_penalty(a.w - pa.w, K.diff_gain, K.diff_exp));
+  const float diff_penalty = sum4(gain_exp_penalty(a.x - pa.x, K.diff_gain, K.diff_exp), gain_exp_penalty(a.y - pa.y, K.diff_gain, K.diff_exp),
+                                  gain_exp_penalty(a.z - pa.z, K.diff_gain, K.diff_exp), gain_exp_penalty(a.w - pa.w, K.diff_gain, K.diff_exp));
   return towards_goal_reward + (pos_reward * (((alignment_reward + vel_reward) + angvel_reward) + diff_penalty) +
                                 ((((angvel_reward + vel_reward) + upright_reward) + pos_reward) + action_cost)) / K.divisor;  // :305
 }
@@ -76,12 +68,12 @@ __global__ void __launch_bounds__(256) k_e2e_reward(AgxEnvBuffers B, int n, cons
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   bool reset = false;
   if (i < n) {
-    const V3 p = V3{E2E_AT(B.state, 0), E2E_AT(B.state, 1), E2E_AT(B.state, 2)};
-    const Q4 q = Q4{E2E_AT(B.state, 3), E2E_AT(B.state, 4), E2E_AT(B.state, 5), E2E_AT(B.state, 6)};
-    const V3 v = V3{E2E_AT(B.state, 7), E2E_AT(B.state, 8), E2E_AT(B.state, 9)};
-    const V3 w = V3{E2E_AT(B.derived, 13), E2E_AT(B.derived, 14), E2E_AT(B.derived, 15)};
-    const V3 err = V3{E2E_AT(target, 0), E2E_AT(target, 1), E2E_AT(target, 2)} - p;
-    const V3 perr = V3{E2E_AT(prev_pos_error, 0), E2E_AT(prev_pos_error, 1), E2E_AT(prev_pos_error, 2)};
+    const V3 p = V3{AGX_TASK_AT(B.state, 0), AGX_TASK_AT(B.state, 1), AGX_TASK_AT(B.state, 2)};
+    const Q4 q = Q4{AGX_TASK_AT(B.state, 3), AGX_TASK_AT(B.state, 4), AGX_TASK_AT(B.state, 5), AGX_TASK_AT(B.state, 6)};
+    const V3 v = V3{AGX_TASK_AT(B.state, 7), AGX_TASK_AT(B.state, 8), AGX_TASK_AT(B.state, 9)};
+    const V3 w = V3{AGX_TASK_AT(B.derived, 13), AGX_TASK_AT(B.derived, 14), AGX_TASK_AT(B.derived, 15)};
+    const V3 err = V3{AGX_TASK_AT(target, 0), AGX_TASK_AT(target, 1), AGX_TASK_AT(target, 2)} - p;
+    const V3 perr = V3{AGX_TASK_AT(prev_pos_error, 0), AGX_TASK_AT(prev_pos_error, 1), AGX_TASK_AT(prev_pos_error, 2)};
     const float4 a = *reinterpret_cast<const float4 *>(actions + (size_t)i * 4);
     const float4 pa = *reinterpret_cast<const float4 *>(prev_actions + (size_t)i * 4);
     const float dist = norm(err);
@@ -89,23 +81,12 @@ __global__ void __launch_bounds__(256) k_e2e_reward(AgxEnvBuffers B, int n, cons
     bool crash = B.crashes[i] != 0;
     if (dist > crash_dist) crash = true;  // :307
     B.crashes[i] = crash ? 1 : 0;
-    const bool trunc = B.sim_steps[i] > episode_len;
-    B.truncations[i] = trunc ? 1 : 0;
-    reset = (crash && reset_on_collision) || trunc;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = reset_set_truncate(B, i, crash, episode_len, reset_on_collision);
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // ---- the observation ----------------------------------------------------------------------------------------------------
-// two standard normals from two uniforms (Box-Muller, as agx_imu.hip draws them); 1 - u keeps the log argument in (0, 1]
-AGX_DEV void e2e_normal_pair(float u1, float u2, float &z0, float &z1) {
-  const float r = sqrtf(-2.0f * logf(1.0f - u1));
-  float sn, cs;
-  sincos_bounded(kTwoPi * u2, sn, cs);
-  z0 = r * cs;
-  z1 = r * sn;
-}
 // The twelve standard normals of one env's observation, in the reference's draw order (position, orientation, linear velocity,
 // body angular velocity: :207-218), three each.  Host: z [4][N][3].  Device generator: stream RNG_E2E_OBS_NOISE of
 // (seed; GLOBAL env index, env step), blocks 0-2 -> 12 uniforms -> 6 pairs.
@@ -124,7 +105,7 @@ AGX_DEV E2ENoise e2e_noise(const AgxEnvBuffers &B, int n, int i, const float *__
     float u[12];
     rng_fill<12>(B.rng_seed, B.env_index_base + i, agx::step_index(B), RNG_E2E_OBS_NOISE, u);
 #pragma unroll
-    for (int j = 0; j < 6; ++j) e2e_normal_pair(u[2 * j], u[2 * j + 1], N.z[2 * j], N.z[2 * j + 1]);
+    for (int j = 0; j < 6; ++j) normal_pair(u[2 * j], u[2 * j + 1], N.z[2 * j], N.z[2 * j + 1]);
   }
   return N;
 }
@@ -171,10 +152,10 @@ AGX_DEV void e2e_write_obs(V3 err, Q4 q, V3 v, V3 w, const E2ENoise &N, float *_
 }
 // ... on the tensors as they stand in memory
 AGX_DEV void e2e_observe(const AgxEnvBuffers &B, int n, int i, V3 tgt, const float *__restrict__ z, float *__restrict__ obs) {
-  const V3 p = V3{E2E_AT(B.state, 0), E2E_AT(B.state, 1), E2E_AT(B.state, 2)};
-  const Q4 q = Q4{E2E_AT(B.state, 3), E2E_AT(B.state, 4), E2E_AT(B.state, 5), E2E_AT(B.state, 6)};
-  const V3 v = V3{E2E_AT(B.state, 7), E2E_AT(B.state, 8), E2E_AT(B.state, 9)};
-  const V3 w = V3{E2E_AT(B.derived, 13), E2E_AT(B.derived, 14), E2E_AT(B.derived, 15)};
+  const V3 p = task_vec(B.state, 0, n, i);
+  const Q4 q = task_quat(B.state, 3, n, i);
+  const V3 v = task_vec(B.state, 7, n, i);
+  const V3 w = task_vec(B.derived, 13, n, i);
   e2e_write_obs(tgt - p, q, v, w, e2e_noise(B, n, i, z), obs + (size_t)i * 15);
 }
 
@@ -182,7 +163,7 @@ __global__ void __launch_bounds__(256) k_e2e_obs(AgxEnvBuffers B, int n, const f
                                                   float *__restrict__ obs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  e2e_observe(B, n, i, V3{E2E_AT(target, 0), E2E_AT(target, 1), E2E_AT(target, 2)}, z, obs);
+  e2e_observe(B, n, i, task_vec(target, 0, n, i), z, obs);
 }
 
 // the normals themselves, [4][N][3]: what k_e2e_obs with z == NULL scales and adds
@@ -216,7 +197,7 @@ __global__ void __launch_bounds__(256) k_e2e_post_step(AgxRobotParams P, AgxEnvB
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (valid) {
     s = load_state(B.state, n, i);
-    tgt = V3{E2E_AT(target, 0), E2E_AT(target, 1), E2E_AT(target, 2)};
+    tgt = task_vec(target, 0, n, i);
     mask = B.reset_mask[i];
     if (B.episode_count) ep = B.episode_count[i];
     a = *reinterpret_cast<const float4 *>(actions + (size_t)i * 4);
@@ -227,34 +208,23 @@ __global__ void __launch_bounds__(256) k_e2e_post_step(AgxRobotParams P, AgxEnvB
   if (!valid) return;
   if (any) {
     tgt = V3{0.0f, 0.0f, 0.0f};
-    E2E_AT(target, 0) = 0.0f; E2E_AT(target, 1) = 0.0f; E2E_AT(target, 2) = 0.0f;
+    AGX_TASK_AT(target, 0) = 0.0f; AGX_TASK_AT(target, 1) = 0.0f; AGX_TASK_AT(target, 2) = 0.0f;
   }
   __atomic_signal_fence(__ATOMIC_SEQ_CST);  // the loads below stay behind the reset's stores
   e2e_observe(B, n, i, tgt, z, obs);
   *reinterpret_cast<float4 *>(prev_actions + (size_t)i * 4) = a;
-  E2E_AT(prev_pos_error, 0) = tgt.x - E2E_AT(B.state, 0);
-  E2E_AT(prev_pos_error, 1) = tgt.y - E2E_AT(B.state, 1);
-  E2E_AT(prev_pos_error, 2) = tgt.z - E2E_AT(B.state, 2);
+  AGX_TASK_AT(prev_pos_error, 0) = tgt.x - AGX_TASK_AT(B.state, 0);
+  AGX_TASK_AT(prev_pos_error, 1) = tgt.y - AGX_TASK_AT(B.state, 1);
+  AGX_TASK_AT(prev_pos_error, 2) = tgt.z - AGX_TASK_AT(B.state, 2);
 }
 
-#undef E2E_AT
 }  // namespace agx
-
-static int e2e_check(const char *what, const AgxEnvBuffers *B, int n) {
-  AGX_REQUIRE(B != nullptr, "%s: null buffers", what);
-  AGX_REQUIRE(n > 0, "%s: num_envs must be > 0 (got %d)", what, n);
-  AGX_REQUIRE(n <= (1 << 26), "%s: num_envs %d above 2^26 per GPU: shard the job", what, n);
-  AGX_REQUIRE(B->state != nullptr, "%s: buf->state is not set", what);
-  return AGX_OK;
-}
-// the [N][4] action tensors are moved as one 16-byte access per env
-static bool e2e_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 extern "C" int agx_end_to_end_pre_step(const AgxEnvBuffers *B, int n, const float *actions_in, const AgxEndToEndLimits *limits,
                                        float *actions, float *prev_position, void *stream) {
-  if (int e = e2e_check("agx_end_to_end_pre_step", B, n)) return e;
+  if (int e = task_check("agx_end_to_end_pre_step", B, n)) return e;
   AGX_REQUIRE(actions_in && limits && actions && prev_position, "agx_end_to_end_pre_step: null argument");
-  AGX_REQUIRE(e2e_aligned16(actions_in) && e2e_aligned16(actions), "agx_end_to_end_pre_step: the [N][4] action tensors must be 16-byte aligned");
+  AGX_REQUIRE(aligned16(actions_in) && aligned16(actions), "agx_end_to_end_pre_step: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   hipLaunchKernelGGL(k_e2e_pre_step, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n, actions_in, *limits, actions,
                      prev_position);
@@ -264,12 +234,11 @@ extern "C" int agx_end_to_end_pre_step(const AgxEnvBuffers *B, int n, const floa
 extern "C" int agx_end_to_end_reward(const AgxEnvBuffers *B, int n, const float *target, const float *actions, const float *prev_actions,
                                      const float *prev_pos_error, const AgxEndToEndReward *constants, float crash_dist, int episode_len,
                                      int reset_on_collision, float *reward, void *stream) {
-  if (int e = e2e_check("agx_end_to_end_reward", B, n)) return e;
-  AGX_REQUIRE(B->flag_parity == 0 || B->flag_parity == 1, "agx_end_to_end_reward: flag_parity must be 0 or 1");
+  if (int e = task_check("agx_end_to_end_reward", B, n, true)) return e;
   AGX_REQUIRE(target && actions && prev_actions && prev_pos_error && constants && reward && B->derived && B->crashes && B->truncations &&
                   B->sim_steps && B->reset_mask && B->reset_flag,
               "agx_end_to_end_reward: null argument");
-  AGX_REQUIRE(e2e_aligned16(actions) && e2e_aligned16(prev_actions), "agx_end_to_end_reward: the [N][4] action tensors must be 16-byte aligned");
+  AGX_REQUIRE(aligned16(actions) && aligned16(prev_actions), "agx_end_to_end_reward: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   hipLaunchKernelGGL(k_e2e_reward, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *B, n, target, actions, prev_actions,
                      prev_pos_error, *constants, crash_dist, episode_len, reset_on_collision, reward);
@@ -277,7 +246,7 @@ extern "C" int agx_end_to_end_reward(const AgxEnvBuffers *B, int n, const float 
 }
 
 extern "C" int agx_end_to_end_obs(const AgxEnvBuffers *B, int n, const float *target, const float *noise, float *obs, void *stream) {
-  if (int e = e2e_check("agx_end_to_end_obs", B, n)) return e;
+  if (int e = task_check("agx_end_to_end_obs", B, n)) return e;
   AGX_REQUIRE(target && obs && B->derived, "agx_end_to_end_obs: null argument");
   AGX_REQUIRE(!B->step_rows[0] && !B->step_rows[1], "agx_end_to_end_obs: exchange rows (step_rows) are not written for the 15-D observation");
   const int block = pick_block(n);
@@ -300,7 +269,7 @@ extern "C" int agx_post_step_end_to_end(const AgxRobotParams *P, const AgxEnvBuf
   AGX_REQUIRE(!B->step_rows[0] && !B->step_rows[1], "agx_post_step_end_to_end: exchange rows (step_rows) are not written for the 15-D observation");
   AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_LEAN) == 0, "agx_post_step_end_to_end: the observation reads robot_body_angvel, which the lean step does not maintain");
   AGX_REQUIRE((B->launch_flags & AGX_LAUNCH_ROV) == 0, "AGX_LAUNCH_ROV: agx_post_step_end_to_end resets multirotors only (use agx_reset_masked)");
-  AGX_REQUIRE(e2e_aligned16(actions) && e2e_aligned16(prev_actions), "agx_post_step_end_to_end: the [N][4] action tensors must be 16-byte aligned");
+  AGX_REQUIRE(aligned16(actions) && aligned16(prev_actions), "agx_post_step_end_to_end: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   AGX_DISPATCH_M(P->num_motors, hipLaunchKernelGGL((k_e2e_post_step<kM>), dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, *P,
                                                    *B, n, *R, target, noise, obs, actions, prev_actions, prev_pos_error));

@@ -1,12 +1,9 @@
 #pragma once
 // Task code: the position / navigation rewards and the navigation bookkeeping as device functions (the fused env steps run them as
 // their epilogue), the observation writers, and the stand-alone reward and observation kernels with their entry points.
-// Part of the one translation unit agx_dynamics.hip, which alone includes it (after the AGX_DYN_* switches).
+// Part of the one translation unit agx_dynamics.hip, which alone includes it (after the AGX_DYN_* switches and agx_task_parts.h).
 
 namespace agx {
-AGX_DEV float exp_reward(float mag, float ex, float v) { return mag * exp_cw(-(v * v) * ex); }
-AGX_DEV float exp_penalty(float mag, float ex, float v) { return mag * (exp_cw(-(v * v) * ex) - 1.0f); }
-
 // position_setpoint_task.py:245-282 on registers; returns the reward, ORs the distance crash
 AGX_DEV float reward_position(const EnvState &s, Q4 qveh, V3 wb, V3 tgt, bool &crash) {
   V3 pe = quat_apply(conj(qveh), tgt - s.p);  // quat_apply_inverse
@@ -80,21 +77,12 @@ __global__ void __launch_bounds__(256) k_reward_position(AgxEnvBuffers B, int n,
     bool crash = B.crashes[i] != 0;
     reward[i] = reward_position(s, qveh, wb, tgt, crash);
     B.crashes[i] = crash ? 1 : 0;
-    bool trunc = B.sim_steps[i] > episode_len;
-    B.truncations[i] = trunc ? 1 : 0;
-    reset = (crash && reset_on_collision) || trunc;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = reset_set_truncate(B, i, crash, episode_len, reset_on_collision);
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // position_setpoint_task.py:194-203, obs [N][13] row-major (what the policy network consumes)
-// reward | terminated | truncated behind the observation in the exchange row (header: step_rows)
-AGX_DEV void write_step_row_tail(const AgxEnvBuffers &B, int i, float *__restrict__ row, int obs_dim) {
-  row_store(B, row + obs_dim, B.step_reward[i]);
-  row_store(B, row + obs_dim + 1, B.crashes[i] ? 1.0f : 0.0f);
-  row_store(B, row + obs_dim + 2, B.truncations[i] ? 1.0f : 0.0f);
-}
 AGX_DEV void write_obs_position(const AgxEnvBuffers &B, int n, int i, V3 tgt, float *__restrict__ obs, const EnvState &s,
                                 const Derived &d) {
   float v[13] = {tgt.x - s.p.x, tgt.y - s.p.y, tgt.z - s.p.z, s.q.x, s.q.y, s.q.z, s.q.w,
@@ -147,12 +135,9 @@ __global__ void __launch_bounds__(256) k_reward_navigation(AgxEnvBuffers B, int 
     bool crash = B.crashes[i] != 0;
     reward[i] = reward_navigation(R.rp, cpf, pe, ppe, AGX_AT(B.actions, 0), AGX_AT(B.actions, 2), AGX_AT(B.actions, 3),
                                   AGX_AT(B.prev_actions, 0), AGX_AT(B.prev_actions, 2), AGX_AT(B.prev_actions, 3), crash);
-    bool trunc = B.sim_steps[i] > episode_len;
-    B.truncations[i] = trunc ? 1 : 0;
-    reset = (crash && reset_on_collision) || trunc;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = reset_set_truncate(B, i, crash, episode_len, reset_on_collision);
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // navigation_task.py:369-393; one wave per env so the depth min-pool is a coalesced sweep

@@ -143,6 +143,7 @@ static bool quad_loop_kernel_usable(const AgxRobotParams *P, const AgxEnvBuffers
 
 #include "agx_dyn_state.h"
 #include "agx_dyn_physics.h"
+#include "agx_task_parts.h"
 #include "agx_dyn_task.h"
 #include "agx_dyn_env_step.h"
 #include "agx_dyn_quad.h"

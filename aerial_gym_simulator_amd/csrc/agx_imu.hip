@@ -1,21 +1,11 @@
 // IMU sensor (aerial_gym/sensors/imu_sensor.py): specific force + body rates with a bias random walk,
 // white noise, mount misalignment and saturation.  One lane per env; the k physics sub-steps of the env
 // step are folded into one launch (k bias increments, last sub-step's noise and measurement).
-#include "agx_common.h"
-#include "agx_device_math.h"
 #include "agx_rng.h"
-#include "agx_step_signal.h"
+#include "agx_task_parts.h"
 
 namespace agx {
 
-// two standard normals from two uniforms (Box-Muller); 1 - u keeps the log argument in (0, 1]
-AGX_DEV void normal_pair(float u1, float u2, float &z0, float &z1) {
-  float r = sqrtf(-2.0f * logf(1.0f - u1));
-  float sn, cs;
-  sincos_bounded(kTwoPi * u2, sn, cs);
-  z0 = r * cs;
-  z1 = r * sn;
-}
 // 6 normals of (env, step, sub-step, which): Philox blocks 3*slot .. 3*slot+2 -> 12 uniforms -> 6 normals
 AGX_DEV void normals6(uint64_t seed, int env, int step, int slot, float z[6]) {
   float u[12];

@@ -16,15 +16,10 @@
 //
 // All three are epilogue work on data the env-step and ray-cast kernels left in HBM: one pass each,
 // HBM bound (the image kernel reads the 69 KB point cloud of an env exactly once).
-#include "agx_common.h"
-#include "agx_device_math.h"
 #include "agx_rng.h"
-#include "agx_step_signal.h"
+#include "agx_task_parts.h"
 
 namespace agx {
-
-AGX_DEV float exp_reward(float mag, float ex, float v) { return mag * exp_cw(-(v * v) * ex); }
-AGX_DEV float exp_penalty(float mag, float ex, float v) { return mag * (exp_cw(-(v * v) * ex) - 1.0f); }
 
 struct LidarNavParams {
   float rp[22];
@@ -237,12 +232,9 @@ __global__ void __launch_bounds__(256) k_reward_lidar_navigation(AgxEnvBuffers B
     if (crash) r = rp[21];
     reward[i] = r;
 
-    bool trunc = B.sim_steps[i] > episode_len;
-    B.truncations[i] = trunc ? 1 : 0;
-    reset = (crash && reset_on_collision) || trunc;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = reset_set_truncate(B, i, crash, episode_len, reset_on_collision);
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // one wave per env: lane 0 writes the 17 state entries, all lanes copy the pooled LiDAR cells
@@ -288,8 +280,8 @@ AGX_DEV void obs_lidar_navigation_env(const AgxEnvBuffers &B, int n, int i, cons
     if (row) {
 #pragma unroll
       for (int c = 0; c < 17; ++c) row_store(B, row + c, s[c]);
-      row_store(B, row + obs_dim, B.step_reward[i]);
-      row_store(B, row + obs_dim + 1, B.crashes[i] ? 1.0f : 0.0f);
+      row_store(B, row + obs_dim, B.step_reward[i]);  // (write_step_row_tail, kept spelled out: through the helper's __restrict__
+      row_store(B, row + obs_dim + 1, B.crashes[i] ? 1.0f : 0.0f);  //  row the kernel's registers are allocated differently)
       row_store(B, row + obs_dim + 2, B.truncations[i] ? 1.0f : 0.0f);
     }
   }

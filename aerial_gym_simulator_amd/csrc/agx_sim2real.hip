@@ -5,17 +5,9 @@
 // caller hands to task.step() is one of them).  Every + - * / sqrt is one IEEE operation in the reference's order (the
 // library is compiled with -ffp-contract=off); exp / sin / cos / atan2 / asin are the correctly rounded ones of
 // agx_device_math.h; torch.norm, torch.cross and the quat_* helpers are the forms restated there.
-#include "agx_common.h"
-#include "agx_device_math.h"
+#include "agx_task_parts.h"
 
 namespace agx {
-
-#define S2R_AT(p, c) (p)[(size_t)(c) * (size_t)n + (size_t)i]
-
-AGX_DEV V3 s2r_vec(const float *__restrict__ p, int c0, int n, int i) { return V3{S2R_AT(p, c0), S2R_AT(p, c0 + 1), S2R_AT(p, c0 + 2)}; }
-AGX_DEV Q4 s2r_quat(const float *__restrict__ p, int c0, int n, int i) {
-  return Q4{S2R_AT(p, c0), S2R_AT(p, c0 + 1), S2R_AT(p, c0 + 2), S2R_AT(p, c0 + 3)};
-}
 
 // step() up to sim_env.step (velocity :157-161, acceleration :161-170), in the reference's order: prev_actions <- what
 // task.actions reads NOW (`before`: the tensor of the previous call, which the caller may have overwritten since -- it may be
@@ -29,10 +21,10 @@ __global__ void __launch_bounds__(256) k_sim2real_pre_step(int kind, AgxEnvBuffe
   if (i >= n) return;
   const float4 pa = *reinterpret_cast<const float4 *>(before + (size_t)i * 4);
   *reinterpret_cast<float4 *>(prev_actions + (size_t)i * 4) = pa;
-  const V3 d = s2r_vec(target, 0, n, i) - s2r_vec(B.state, 0, n, i);
+  const V3 d = task_vec(target, 0, n, i) - task_vec(B.state, 0, n, i);
   prev_dist[i] = norm(d);
   if (kind == AGX_SIM2REAL_ACCELERATION) {
-    const V3 r = quat_rotate(s2r_quat(B.state, 3, n, i), V3{pa.x, pa.y, pa.z});
+    const V3 r = quat_rotate(task_quat(B.state, 3, n, i), V3{pa.x, pa.y, pa.z});
     *reinterpret_cast<float4 *>(prev_actions_vehicle + (size_t)i * 4) = make_float4(r.x, r.y, r.z, pa.w);
     float4 a = *reinterpret_cast<const float4 *>(actions + (size_t)i * 4);
     a.x = 2.0f * a.x; a.y = 2.0f * a.y; a.z = 2.0f * a.z;
@@ -40,24 +32,17 @@ __global__ void __launch_bounds__(256) k_sim2real_pre_step(int kind, AgxEnvBuffe
   }
 }
 
-// gain * exp(-e * x * x), gain * exp(-e * |x|), gain * (exp(-e * |x|) - 1): exp_func / abs_exp_func / abs_exp_penalty_func
-AGX_DEV float s2r_exp(float x, float gain, float e) { return gain * exp_cw((-e * x) * x); }
-AGX_DEV float s2r_abs_exp(float x, float gain, float e) { return gain * exp_cw(-e * fabsf(x)); }
-AGX_DEV float s2r_abs_exp_penalty(float x, float gain, float e) { return gain * (exp_cw(-e * fabsf(x)) - 1.0f); }
-// torch.sum(x, dim=1) of four columns
-AGX_DEV float s2r_sum4(float a, float b, float c, float d) { return ((a + b) + c) + d; }
-
 // compute_reward of the velocity task (position_setpoint_task_sim2real.py:286-339)
 AGX_DEV float s2r_reward_velocity(float dist, float prev_dist, float yaw_error, float speed, float4 a, float4 p) {
-  const float pos_reward = (s2r_exp(dist, 2.0f, 1.0f) + s2r_exp(dist, 3.0f, 10.0f)) + s2r_abs_exp(dist, 3.0f, 50.0f);
-  const float speed_reward = s2r_exp(speed, 1.0f, 3.0f);
+  const float pos_reward = (gain_exp(dist, 2.0f, 1.0f) + gain_exp(dist, 3.0f, 10.0f)) + gain_abs_exp(dist, 3.0f, 50.0f);
+  const float speed_reward = gain_exp(speed, 1.0f, 3.0f);
   const float dist_reward = (20.0f - dist) / 40.0f;
-  const float action_penalty = s2r_sum4(s2r_abs_exp_penalty(a.x, 0.2f, 4.0f), s2r_abs_exp_penalty(a.y, 0.2f, 4.0f),
-                                        s2r_abs_exp_penalty(a.z, 0.2f, 4.0f), s2r_abs_exp_penalty(a.w, 0.2f, 4.0f));
-  const float diff_penalty = s2r_sum4(s2r_abs_exp_penalty(a.x - p.x, 0.3f, 6.0f), s2r_abs_exp_penalty(a.y - p.y, 0.3f, 6.0f),
-                                      s2r_abs_exp_penalty(a.z - p.z, 0.3f, 6.0f), s2r_abs_exp_penalty(a.w - p.w, 0.3f, 6.0f));
+  const float action_penalty = sum4(gain_abs_exp_penalty(a.x, 0.2f, 4.0f), gain_abs_exp_penalty(a.y, 0.2f, 4.0f),
+                                    gain_abs_exp_penalty(a.z, 0.2f, 4.0f), gain_abs_exp_penalty(a.w, 0.2f, 4.0f));
+  const float diff_penalty = sum4(gain_abs_exp_penalty(a.x - p.x, 0.3f, 6.0f), gain_abs_exp_penalty(a.y - p.y, 0.3f, 6.0f),
+                                  gain_abs_exp_penalty(a.z - p.z, 0.3f, 6.0f), gain_abs_exp_penalty(a.w - p.w, 0.3f, 6.0f));
   const float closer_reward = 400.0f * (prev_dist - dist);
-  const float yaw_reward = s2r_abs_exp(yaw_error, 2.0f, 3.0f);
+  const float yaw_reward = gain_abs_exp(yaw_error, 2.0f, 3.0f);
   float total = (pos_reward + dist_reward) + pos_reward * ((speed_reward + action_penalty) + closer_reward / 10.0f);
   total = total + action_penalty;
   total = total + diff_penalty;
@@ -69,16 +54,16 @@ AGX_DEV float s2r_reward_velocity(float dist, float prev_dist, float yaw_error, 
 // compute_reward of the acceleration task (position_setpoint_task_acceleration_sim2real.py:300-356): other constants, the
 // two-sided closer_reward, actions in the vehicle frame
 AGX_DEV float s2r_reward_acceleration(float dist, float prev_dist, float yaw_error, float speed, float4 a, float4 p) {
-  const float pos_reward = (s2r_exp(dist, 2.0f, 1.0f) + s2r_exp(dist, 3.0f, 10.0f)) + s2r_abs_exp(dist, 3.0f, 50.0f);
-  const float close_pos_reward = s2r_exp(dist, 2.0f, 1.0f);
-  const float speed_reward = s2r_exp(speed, 2.0f, 2.5f);
-  const float action_penalty = s2r_sum4(s2r_abs_exp_penalty(a.x, 0.3f, 4.0f), s2r_abs_exp_penalty(a.y, 0.3f, 4.0f),
-                                        s2r_abs_exp_penalty(a.z, 0.3f, 4.0f), s2r_abs_exp_penalty(a.w, 0.3f, 4.0f));
-  const float diff_penalty = s2r_sum4(s2r_abs_exp_penalty(a.x - p.x, 0.4f, 6.0f), s2r_abs_exp_penalty(a.y - p.y, 0.4f, 6.0f),
-                                      s2r_abs_exp_penalty(a.z - p.z, 0.4f, 6.0f), s2r_abs_exp_penalty(a.w - p.w, 0.4f, 6.0f));
+  const float pos_reward = (gain_exp(dist, 2.0f, 1.0f) + gain_exp(dist, 3.0f, 10.0f)) + gain_abs_exp(dist, 3.0f, 50.0f);
+  const float close_pos_reward = gain_exp(dist, 2.0f, 1.0f);
+  const float speed_reward = gain_exp(speed, 2.0f, 2.5f);
+  const float action_penalty = sum4(gain_abs_exp_penalty(a.x, 0.3f, 4.0f), gain_abs_exp_penalty(a.y, 0.3f, 4.0f),
+                                    gain_abs_exp_penalty(a.z, 0.3f, 4.0f), gain_abs_exp_penalty(a.w, 0.3f, 4.0f));
+  const float diff_penalty = sum4(gain_abs_exp_penalty(a.x - p.x, 0.4f, 6.0f), gain_abs_exp_penalty(a.y - p.y, 0.4f, 6.0f),
+                                  gain_abs_exp_penalty(a.z - p.z, 0.4f, 6.0f), gain_abs_exp_penalty(a.w - p.w, 0.4f, 6.0f));
   const float closer = prev_dist - dist;
   const float closer_reward = (dist < prev_dist) ? 400.0f * closer : 1200.0f * closer;
-  const float yaw_reward = s2r_abs_exp(yaw_error, 3.0f, 5.0f);
+  const float yaw_reward = gain_abs_exp(yaw_error, 3.0f, 5.0f);
   float total = pos_reward + pos_reward * ((closer_reward / 9.0f + action_penalty / 3.0f) + speed_reward / 1.5f);
   total = total + action_penalty;
   total = total + diff_penalty;
@@ -100,11 +85,11 @@ __global__ void __launch_bounds__(256) k_sim2real_reward(int kind, AgxEnvBuffers
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   bool reset = false;
   if (i < n) {
-    const V3 p = s2r_vec(B.state, 0, n, i);
-    const Q4 q = s2r_quat(B.state, 3, n, i);
-    const Q4 qveh = s2r_quat(B.derived, 3, n, i);
-    const V3 vbody = s2r_vec(B.derived, 10, n, i);
-    const V3 err = s2r_vec(target, 0, n, i) - p;
+    const V3 p = task_vec(B.state, 0, n, i);
+    const Q4 q = task_quat(B.state, 3, n, i);
+    const Q4 qveh = task_quat(B.derived, 3, n, i);
+    const V3 vbody = task_vec(B.derived, 10, n, i);
+    const V3 err = task_vec(target, 0, n, i) - p;
     const float4 a = *reinterpret_cast<const float4 *>(actions + (size_t)i * 4);
     const float yaw_error = 0.0f - ssa(yaw_0_2pi(q));
     const float speed = norm(vbody);
@@ -127,12 +112,9 @@ __global__ void __launch_bounds__(256) k_sim2real_reward(int kind, AgxEnvBuffers
     if (crash) total = -50.0f;
     reward[i] = total;
     B.crashes[i] = crash ? 1 : 0;
-    const bool trunc = B.sim_steps[i] > episode_len;
-    B.truncations[i] = trunc ? 1 : 0;
-    reset = (crash && reset_on_collision) || trunc;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = reset_set_truncate(B, i, crash, episode_len, reset_on_collision);
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // process_obs_for_task (:202-228 / :211-237, the same in both tasks): the state quaternion times sign(w), STORED BACK into
@@ -144,38 +126,32 @@ __global__ void __launch_bounds__(256) k_sim2real_obs(AgxEnvBuffers B, int n, co
                                                        const float *__restrict__ z, float *__restrict__ obs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const V3 err = s2r_vec(target, 0, n, i) - s2r_vec(B.state, 0, n, i);
-  Q4 q = s2r_quat(B.state, 3, n, i);
+  const V3 err = task_vec(target, 0, n, i) - task_vec(B.state, 0, n, i);
+  Q4 q = task_quat(B.state, 3, n, i);
   const float s = (float)(q.w > 0.0f) - (float)(q.w < 0.0f);
   q = Q4{s * q.x, s * q.y, s * q.z, s * q.w};
   float *st = const_cast<float *>(B.state);
-  S2R_AT(st, 3) = q.x; S2R_AT(st, 4) = q.y; S2R_AT(st, 5) = q.z; S2R_AT(st, 6) = q.w;
+  AGX_TASK_AT(st, 3) = q.x; AGX_TASK_AT(st, 4) = q.y; AGX_TASK_AT(st, 5) = q.z; AGX_TASK_AT(st, 6) = q.w;
   const float *ze = z + (size_t)i * 3, *zp = ze + (size_t)n * 3, *zv = zp + (size_t)n * 3, *zw = zv + (size_t)n * 3;
   const V3 e = euler_xyz_0_2pi(q);
   const Q4 qn = quat_from_euler(ssa(e.x) + ze[0] * 0.02f, ssa(e.y) + ze[1] * 0.02f, ssa(e.z) + ze[2] * 0.02f);
-  const V3 vb = s2r_vec(B.derived, 10, n, i), wb = s2r_vec(B.derived, 13, n, i);
+  const V3 vb = task_vec(B.derived, 10, n, i), wb = task_vec(B.derived, 13, n, i);
   float *of = obs + (size_t)i * 17;  // rows of 17 floats: 4-byte aligned only
   of[0] = err.x + zp[0] * 0.03f; of[1] = err.y + zp[1] * 0.03f; of[2] = err.z + zp[2] * 0.03f;
   of[3] = qn.x; of[4] = qn.y; of[5] = qn.z; of[6] = qn.w;
   of[7] = vb.x + zv[0] * 0.02f; of[8] = vb.y + zv[1] * 0.02f; of[9] = vb.z + zv[2] * 0.02f;
   of[10] = wb.x + zw[0] * 0.02f; of[11] = wb.y + zw[1] * 0.02f; of[12] = wb.z + zw[2] * 0.02f;
-  of[13] = S2R_AT(B.actions, 0); of[14] = S2R_AT(B.actions, 1); of[15] = S2R_AT(B.actions, 2); of[16] = S2R_AT(B.actions, 3);
+  of[13] = AGX_TASK_AT(B.actions, 0); of[14] = AGX_TASK_AT(B.actions, 1); of[15] = AGX_TASK_AT(B.actions, 2); of[16] = AGX_TASK_AT(B.actions, 3);
 }
 
 }  // namespace agx
 
 using namespace agx;
 
-static int s2r_check(const char *what, int kind, const AgxEnvBuffers *B, int n) {
+static int s2r_check(const char *what, int kind, const AgxEnvBuffers *B, int n, bool publishes_reset_set = false) {
   AGX_REQUIRE(kind == AGX_SIM2REAL_VELOCITY || kind == AGX_SIM2REAL_ACCELERATION, "%s: kind %d", what, kind);
-  AGX_REQUIRE(B != nullptr, "%s: null buffers", what);
-  AGX_REQUIRE(n > 0, "%s: num_envs must be > 0 (got %d)", what, n);
-  AGX_REQUIRE(n <= (1 << 26), "%s: num_envs %d above 2^26 per GPU: shard the job", what, n);
-  AGX_REQUIRE(B->state != nullptr, "%s: buf->state is not set", what);
-  return AGX_OK;
+  return task_check(what, B, n, publishes_reset_set);
 }
-// the [N][4] action tensors are moved as one 16-byte access per env
-static bool s2r_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 extern "C" int agx_sim2real_pre_step(int kind, const AgxEnvBuffers *B, int n, const float *target, const float *actions_before,
                                      float *actions, float *prev_actions, float *prev_dist, float *prev_actions_vehicle_frame,
@@ -184,8 +160,8 @@ extern "C" int agx_sim2real_pre_step(int kind, const AgxEnvBuffers *B, int n, co
   AGX_REQUIRE(target && actions_before && actions && prev_actions && prev_dist, "agx_sim2real_pre_step: null buffer");
   AGX_REQUIRE(kind != AGX_SIM2REAL_ACCELERATION || prev_actions_vehicle_frame,
               "agx_sim2real_pre_step: the acceleration task needs prev_actions_vehicle_frame");
-  AGX_REQUIRE(s2r_aligned16(actions_before) && s2r_aligned16(actions) && s2r_aligned16(prev_actions) &&
-                  s2r_aligned16(prev_actions_vehicle_frame),
+  AGX_REQUIRE(aligned16(actions_before) && aligned16(actions) && aligned16(prev_actions) &&
+                  aligned16(prev_actions_vehicle_frame),
               "agx_sim2real_pre_step: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   hipLaunchKernelGGL(k_sim2real_pre_step, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, kind, *B, n, target,
@@ -197,15 +173,14 @@ extern "C" int agx_sim2real_reward(int kind, const AgxEnvBuffers *B, int n, cons
                                    const float *prev_actions, const float *prev_dist, float *actions_vehicle_frame,
                                    const float *prev_actions_vehicle_frame, int episode_len, int reset_on_collision, float *reward,
                                    void *stream) {
-  if (int e = s2r_check("agx_sim2real_reward", kind, B, n)) return e;
-  AGX_REQUIRE(B->flag_parity == 0 || B->flag_parity == 1, "agx_sim2real_reward: flag_parity must be 0 or 1");
+  if (int e = s2r_check("agx_sim2real_reward", kind, B, n, true)) return e;
   AGX_REQUIRE(target && actions && prev_actions && prev_dist && reward && B->derived && B->crashes && B->truncations &&
                   B->sim_steps && B->reset_mask && B->reset_flag,
               "agx_sim2real_reward: null buffer");
   AGX_REQUIRE(kind != AGX_SIM2REAL_ACCELERATION || (actions_vehicle_frame && prev_actions_vehicle_frame),
               "agx_sim2real_reward: the acceleration task needs both vehicle-frame action tensors");
-  AGX_REQUIRE(s2r_aligned16(actions) && s2r_aligned16(prev_actions) && s2r_aligned16(actions_vehicle_frame) &&
-                  s2r_aligned16(prev_actions_vehicle_frame),
+  AGX_REQUIRE(aligned16(actions) && aligned16(prev_actions) && aligned16(actions_vehicle_frame) &&
+                  aligned16(prev_actions_vehicle_frame),
               "agx_sim2real_reward: the [N][4] action tensors must be 16-byte aligned");
   const int block = pick_block(n);
   hipLaunchKernelGGL(k_sim2real_reward, dim3(blocks_for(n, block)), dim3(block), 0, (hipStream_t)stream, kind, *B, n, target, actions,
@@ -215,7 +190,7 @@ extern "C" int agx_sim2real_reward(int kind, const AgxEnvBuffers *B, int n, cons
 }
 
 extern "C" int agx_sim2real_obs(const AgxEnvBuffers *B, int n, const float *target, const float *noise, float *obs, void *stream) {
-  if (int e = s2r_check("agx_sim2real_obs", AGX_SIM2REAL_VELOCITY, B, n)) return e;
+  if (int e = task_check("agx_sim2real_obs", B, n)) return e;
   AGX_REQUIRE(target && noise && obs && B->derived && B->actions, "agx_sim2real_obs: null buffer");
   AGX_REQUIRE(!B->step_rows[0] && !B->step_rows[1], "agx_sim2real_obs: exchange rows (step_rows) are not written for the 17-D observation");
   const int block = pick_block(n);

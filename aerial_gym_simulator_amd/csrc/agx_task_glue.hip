@@ -6,6 +6,7 @@
 #include "agx_device_math.h"
 #include "agx_nav_parts.h"
 #include "agx_rng.h"
+#include "agx_task_parts.h"
 
 namespace agx {
 
@@ -41,10 +42,10 @@ __global__ void __launch_bounds__(256) k_reset_set(AgxEnvBuffers B, int n, int r
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   bool reset = false;
   if (i < n) {
-    reset = (B.crashes[i] != 0 && reset_on_collision != 0) || B.truncations[i] != 0;
-    B.reset_mask[i] = reset ? 1 : 0;
+    reset = (B.crashes[i] != 0 && reset_on_collision != 0) || B.truncations[i] != 0;  // (not reset_set_store: the truncation is
+    B.reset_mask[i] = reset ? 1 : 0;                                                   //  loaded only where the crash does not decide)
   }
-  if (__ballot(reset) != 0ull && (threadIdx.x & 63) == 0) atomicOr(B.reset_flag + B.flag_parity, 1);
+  reset_flag_raise(B, reset);
 }
 
 // last node of a captured env step: the step index the NEXT replay's kernels read (AgxEnvBuffers.step_counter_dev)

@@ -12,12 +12,12 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..sim.sim_builder import SimBuilder
 from ..tensors import aos_view, soa
 from ..utils.logging import CustomLogger
 from ..utils.spaces import Box, Dict
 from ..utils import roctx
 from .base_task import BaseTask
+from .setpoint_task_base import apply_overrides, build_env
 
 logger = CustomLogger("navigation_task")
 
@@ -27,19 +27,12 @@ class NavigationTask(BaseTask):
     _bookkeeping_ptrs = None
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
-        for name, val in (("seed", seed), ("num_envs", num_envs), ("headless", headless), ("device", device),
-                          ("use_warp", use_warp)):
-            if val is not None:
-                setattr(task_config, name, val)
+        apply_overrides(task_config, seed, num_envs, headless, device, use_warp)
         super().__init__(task_config)
         cfg = self.task_config
         self.device = cfg.device
         self._args = dict(cfg.args) if isinstance(cfg.args, dict) else {}  # a snapshot: the config object is shared between tasks
-        self.sim_env = SimBuilder().build_env(
-            sim_name=cfg.sim_name, env_name=cfg.env_name, robot_name=cfg.robot_name,
-            controller_name=cfg.controller_name, args=cfg.args, device=self.device, num_envs=cfg.num_envs,
-            use_warp=cfg.use_warp, headless=cfg.headless,
-        )
+        self.sim_env = build_env(cfg, cfg.args)
         N, dev = self.sim_env.num_envs, self.device
         self.num_envs = N
         self.sim_env.rows_written_twice_per_step = bool(cfg.return_state_before_reset)  # see sharding.StepGather

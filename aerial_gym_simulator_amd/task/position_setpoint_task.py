@@ -1,60 +1,26 @@
 """PositionSetpointTask with the reference's API and step ordering
 (aerial_gym/task/position_setpoint_task/position_setpoint_task.py:21-203); reward, crash,
 truncation and observation packing run in agx_reward_position / agx_obs_position."""
-import numpy as np
 import torch
 
 from .. import _lib
-from ..sim.sim_builder import SimBuilder
-from ..tensors import aos_view, soa
 from ..utils.logging import CustomLogger
-from ..utils.spaces import Box, Dict
 from ..utils import roctx
-from .base_task import BaseTask
+from .setpoint_task_base import SetpointTaskBase
 
 logger = CustomLogger("position_setpoint_task")
 
 
-class PositionSetpointTask(BaseTask):
+class PositionSetpointTask(SetpointTaskBase):
+    OBSERVATION_SPACE_SHAPE = (13,)
+
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
-        for name, val in (("seed", seed), ("num_envs", num_envs), ("headless", headless), ("device", device),
-                          ("use_warp", use_warp)):
-            if val is not None:
-                setattr(task_config, name, val)
-        super().__init__(task_config)
-        cfg = self.task_config
-        self.device = cfg.device
         # args={"lean_step": True} (opt-in, effective above 65 536 envs: EnvManager._enable_lean_step) lets the fused step stop
         # maintaining the tensors that exist only to be looked at through the dict.  Never implied by num_envs: the dict behaves
         # the same at every batch size unless the caller asks otherwise.
-        args = dict(cfg.args) if isinstance(cfg.args, dict) else cfg.args
-        self.sim_env = SimBuilder().build_env(
-            sim_name=cfg.sim_name, env_name=cfg.env_name, robot_name=cfg.robot_name,
-            controller_name=cfg.controller_name, args=args, device=self.device, num_envs=cfg.num_envs,
-            use_warp=cfg.use_warp, headless=cfg.headless,
-        )
-        N, dev = self.sim_env.num_envs, self.device
-        self.num_envs = N
-        self.sim_env.rows_written_twice_per_step = bool(cfg.return_state_before_reset)  # see sharding.StepGather
-        self.actions = torch.zeros((N, cfg.action_space_dim), device=dev)
-        self.prev_actions = torch.zeros_like(self.actions)
-        self.counter = 0
-        self.target_soa = soa(3, N, dev)
-        self.target_position = aos_view(self.target_soa)
-        self.obs_dict = self.sim_env.get_obs()
-        self.obs_dict["num_obstacles_in_env"] = 1
-        self.terminations = self.obs_dict["crashes"]
-        self.truncations = self.obs_dict["truncations"]
-        self.rewards = torch.zeros(N, device=dev)
-        self.observation_space = Dict({"observations": Box(low=-1.0, high=1.0, shape=(13,), dtype=np.float32)})
-        self.action_space = Box(low=-1.0, high=1.0, shape=(cfg.action_space_dim,), dtype=np.float32)
-        self.task_obs = {
-            "observations": torch.zeros((N, cfg.observation_space_dim), device=dev),
-            "priviliged_obs": torch.zeros((N, cfg.privileged_observation_space_dim), device=dev),
-            "collisions": torch.zeros((N, 1), device=dev),
-            "rewards": torch.zeros((N, 1), device=dev),
-        }
-        self.infos = {}
+        args = dict(task_config.args) if isinstance(task_config.args, dict) else task_config.args
+        super().__init__(task_config, seed, num_envs, headless, device, use_warp, env_args=args)
+        self.sim_env.rows_written_twice_per_step = bool(self.task_config.return_state_before_reset)  # see sharding.StepGather
         self._plan = None
         self._proof_watch = self._proof_record = None
         self._fuse_with_env()
@@ -98,9 +64,7 @@ class PositionSetpointTask(BaseTask):
             self._plan_episode_len = T.episode_len
             self._plan_fn = env._lib.agx_position_task_step
             self._action_shape = (env.num_envs, env.num_robot_actions)
-            self.task_obs["rewards"] = self.rewards
-            self.task_obs["terminations"] = self.terminations
-            self.task_obs["truncations"] = self.truncations
+            self._publish_step_flags()
             self._proof_watch = None
             if not env.strict_rng:
                 self._enable_single_launch(plan)
@@ -190,21 +154,7 @@ class PositionSetpointTask(BaseTask):
         if self._plan is not None:
             self._plan.proof_slots = self._plan.proof_record = self._plan.proof_violation = None
         self._free_proof_record()
-        self.sim_env.delete_env()
-
-    def reset(self):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset()
-        return self.get_return_tuple()
-
-    def reset_idx(self, env_ids):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset_idx(env_ids)
-
-    def render(self):
-        return None
+        super().close()
 
     @roctx.ranged("PositionSetpointTask.step")
     def step(self, actions):
@@ -234,15 +184,7 @@ class PositionSetpointTask(BaseTask):
             return (self.task_obs, self.rewards, self.terminations, self.truncations, self.infos)
         if env.task_args is not None:
             env.task_args.episode_len = int(self.task_config.episode_len_steps)
-        env.step(actions=self.actions)
-        self.compute_rewards_and_crashes(self.obs_dict)
-        if self.task_config.return_state_before_reset:
-            return_tuple = self.get_return_tuple()
-        env.post_reward_calculation_step()
-        self.infos = {}
-        if not self.task_config.return_state_before_reset:
-            return_tuple = self.get_return_tuple()
-        return return_tuple
+        return self._step_env_and_return()
 
     def compute_rewards_and_crashes(self, obs_dict):
         """compute_reward + `truncations = sim_steps > episode_len` (reference :205-229,:172-174)."""
@@ -259,16 +201,10 @@ class PositionSetpointTask(BaseTask):
         env.mark_produced(env.RESET_SET)  # the reward kernel wrote this step's reset set
         return self.rewards, self.terminations
 
-    def get_return_tuple(self):
-        self.process_obs_for_task()
-        return (self.task_obs, self.rewards, self.terminations, self.truncations, self.infos)
-
     def process_obs_for_task(self):
         env = self.sim_env
         env._require_device()
-        self.task_obs["rewards"] = self.rewards
-        self.task_obs["terminations"] = self.terminations
-        self.task_obs["truncations"] = self.truncations
+        self._publish_step_flags()
         if env.take_produced(env.OBSERVATION):  # by agx_post_step_position
             return
         _lib.check(

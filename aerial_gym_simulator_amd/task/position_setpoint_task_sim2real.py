@@ -4,86 +4,36 @@ velocity commands) and PositionSetpointTaskAccelerationSim2Real (aerial_gym/task
 position_setpoint_task_acceleration_sim2real/position_setpoint_task_acceleration_sim2real.py:20-273, acceleration commands,
 doubled in the caller's tensor).  Per step() the task side is agx_sim2real_pre_step, agx_sim2real_reward, one normal fill
 and agx_sim2real_obs (csrc/agx_sim2real.hip) around EnvManager.step and the reset launch."""
-import numpy as np
 import torch
 
 from .. import _lib
-from ..sim.sim_builder import SimBuilder
-from ..tensors import aos_view, soa
 from ..utils.logging import CustomLogger
-from ..utils.spaces import Box, Dict
 from ..utils import roctx
-from .base_task import BaseTask
+from .setpoint_task_base import SetpointTaskBase
 
 logger = CustomLogger("position_setpoint_task")
 
 NOISE_TAGS = ("sim2real_obs_noise_euler", "sim2real_obs_noise_pos", "sim2real_obs_noise_linvel", "sim2real_obs_noise_angvel")
 
 
-class PositionSetpointTaskSim2Real(BaseTask):
+class PositionSetpointTaskSim2Real(SetpointTaskBase):
     KIND = _lib.SIM2REAL_VELOCITY
+    OBSERVATION_SPACE_SHAPE = (13,)  # (sic: :95-97)
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
-        for name, val in (("seed", seed), ("num_envs", num_envs), ("headless", headless), ("device", device),
-                          ("use_warp", use_warp)):
-            if val is not None:
-                setattr(task_config, name, val)
-        super().__init__(task_config)
-        cfg = self.task_config
-        self.device = cfg.device
-        for key in cfg.reward_parameters.keys():
-            cfg.reward_parameters[key] = torch.tensor(cfg.reward_parameters[key], device=self.device)
         logger.info("Building environment for position setpoint task.")
-        self.sim_env = SimBuilder().build_env(
-            sim_name=cfg.sim_name, env_name=cfg.env_name, robot_name=cfg.robot_name, controller_name=cfg.controller_name,
-            args=cfg.args, device=self.device, num_envs=cfg.num_envs, use_warp=cfg.use_warp, headless=cfg.headless,
-        )
-        N, dev = self.sim_env.num_envs, self.device
-        self.num_envs = N
+        super().__init__(task_config, seed, num_envs, headless, device, use_warp)
+        cfg, N, dev = self.task_config, self.num_envs, self.device
+        for key in cfg.reward_parameters.keys():
+            cfg.reward_parameters[key] = torch.tensor(cfg.reward_parameters[key], device=dev)
         if cfg.action_space_dim != 4 or cfg.observation_space_dim != 17 or self.sim_env.num_robot_actions != 4:
             raise ValueError("the sim2real set-point tasks have 4-D actions and 17-D observations (task_config.action_space_dim, "
                              "observation_space_dim, the controller's num_actions)")
-        self.actions = torch.zeros((N, cfg.action_space_dim), device=dev)
-        self.prev_actions = torch.zeros_like(self.actions)
         self.prev_actions_vehicle_frame = torch.zeros_like(self.actions)  # (read and written by the acceleration task only)
         self.actions_vehicle_frame = torch.zeros_like(self.actions)
         self.prev_dist = torch.zeros(N, device=dev)
-        self.counter = 0
-        self.target_soa = soa(3, N, dev)
-        self.target_position = aos_view(self.target_soa)
-        self.obs_dict = self.sim_env.get_obs()
-        self.obs_dict["num_obstacles_in_env"] = 1
-        self.terminations = self.obs_dict["crashes"]
-        self.truncations = self.obs_dict["truncations"]
-        self.rewards = torch.zeros(N, device=dev)
-        self.observation_space = Dict({"observations": Box(low=-1.0, high=1.0, shape=(13,), dtype=np.float32)})  # (sic: :95-97)
-        self.action_space = Box(low=-1.0, high=1.0, shape=(cfg.action_space_dim,), dtype=np.float32)
-        self.task_obs = {
-            "observations": torch.zeros((N, cfg.observation_space_dim), device=dev),
-            "priviliged_obs": torch.zeros((N, cfg.privileged_observation_space_dim), device=dev),
-            "collisions": torch.zeros((N, 1), device=dev),
-            "rewards": torch.zeros((N, 1), device=dev),
-        }
         # standard normals of the observation noise, [4][N][3] in the reference's randn_like order (:209-222)
         self.obs_noise = torch.zeros((4, N, 3), device=dev)
-        self.infos = {}
-
-    def close(self):
-        self.sim_env.delete_env()
-
-    def reset(self):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset()
-        return self.get_return_tuple()
-
-    def reset_idx(self, env_ids):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset_idx(env_ids)
-
-    def render(self):
-        return None
 
     def _check_actions(self, actions):
         """The tasks keep the caller's tensor (`self.actions = actions`) and the acceleration task doubles it in place: it has to
@@ -108,20 +58,7 @@ class PositionSetpointTaskSim2Real(BaseTask):
             "agx_sim2real_pre_step",
         )
         self.actions = actions
-        env.step(actions=self.actions)
-        self.compute_rewards_and_crashes(self.obs_dict)  # writes self.rewards and self.terminations (the dict's crashes) in place
-        if self.task_config.return_state_before_reset:
-            return_tuple = self.get_return_tuple()
-        # (truncations = sim_steps > episode_len_steps: written by the reward launch together with the reset set)
-        env.post_reward_calculation_step()
-        self.infos = {}
-        if not self.task_config.return_state_before_reset:
-            return_tuple = self.get_return_tuple()
-        return return_tuple
-
-    def get_return_tuple(self):
-        self.process_obs_for_task()
-        return (self.task_obs, self.rewards, self.terminations, self.truncations, self.infos)
+        return self._step_env_and_return()
 
     def _draw_obs_noise(self):
         env, z = self.sim_env, self.obs_noise
@@ -140,9 +77,7 @@ class PositionSetpointTaskSim2Real(BaseTask):
                                       _lib.dptr(self.task_obs["observations"]), env._stream()),
             "agx_sim2real_obs",
         )
-        self.task_obs["rewards"] = self.rewards
-        self.task_obs["terminations"] = self.terminations
-        self.task_obs["truncations"] = self.truncations
+        self._publish_step_flags()
 
     def compute_rewards_and_crashes(self, obs_dict):
         """compute_reward, the distance crash, `truncations = sim_steps > episode_len_steps` and the step's reset set"""

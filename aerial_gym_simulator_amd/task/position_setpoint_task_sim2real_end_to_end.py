@@ -6,17 +6,14 @@ Per step(), default mode, four launches and no host synchronisation: agx_end_to_
 step, agx_end_to_end_reward (reward, flags, reset set) and agx_post_step_end_to_end (masked reset + observation with device-generator
 noise + prev_actions / prev_pos_error), csrc/agx_dyn_end_to_end.h.  `return_state_before_reset`, an explicit reset() and
 get_return_tuple() by hand take the general path: agx_end_to_end_obs on its own and the env manager's own reset."""
-import numpy as np
 import torch
 
 from .. import _lib
 from ..config import task_config as task_config_module
-from ..sim.sim_builder import SimBuilder
 from ..tensors import aos_view, soa
 from ..utils.logging import CustomLogger
-from ..utils.spaces import Box, Dict
 from ..utils import roctx
-from .base_task import BaseTask
+from .setpoint_task_base import SetpointTaskBase
 
 logger = CustomLogger("position_setpoint_task")
 
@@ -43,27 +40,15 @@ def reward_constants(name):
     return K
 
 
-class PositionSetpointTaskSim2RealEndToEnd(BaseTask):
+class PositionSetpointTaskSim2RealEndToEnd(SetpointTaskBase):
     REWARD = "end_to_end"
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
-        for name, val in (("seed", seed), ("num_envs", num_envs), ("headless", headless), ("device", device),
-                          ("use_warp", use_warp)):
-            if val is not None:
-                setattr(task_config, name, val)
-        super().__init__(task_config)
-        cfg = self.task_config
-        self.device = cfg.device
-        for key in cfg.reward_parameters.keys():
-            cfg.reward_parameters[key] = torch.tensor(cfg.reward_parameters[key], device=self.device)
         logger.info("Building environment for position setpoint task.")
-        self.sim_env = SimBuilder().build_env(
-            sim_name=cfg.sim_name, env_name=cfg.env_name, robot_name=cfg.robot_name, controller_name=cfg.controller_name,
-            args=cfg.args, device=self.device, num_envs=cfg.num_envs, use_warp=cfg.use_warp, headless=cfg.headless,
-        )
-        env = self.sim_env
-        N, dev = env.num_envs, self.device
-        self.num_envs = N
+        super().__init__(task_config, seed, num_envs, headless, device, use_warp)
+        cfg, env, N, dev = self.task_config, self.sim_env, self.num_envs, self.device
+        for key in cfg.reward_parameters.keys():
+            cfg.reward_parameters[key] = torch.tensor(cfg.reward_parameters[key], device=dev)
         if cfg.action_space_dim != 4 or cfg.observation_space_dim != 15 or env.num_robot_actions != 4:
             raise ValueError("the end-to-end set-point task has 4-D actions (one per motor) and 15-D observations "
                              "(task_config.action_space_dim, observation_space_dim, the robot's num_motors)")
@@ -74,32 +59,13 @@ class PositionSetpointTaskSim2RealEndToEnd(BaseTask):
         for j in range(4):
             self._limits.min[j], self._limits.max[j] = float(lo[j]), float(hi[j])
         self._reward_constants = reward_constants(self.REWARD)
-        self.actions = torch.zeros((N, cfg.action_space_dim), device=dev)
-        self.prev_actions = torch.zeros_like(self.actions)
         # never written except to zero on reset (:78-80, :152, handle_action_history has no caller): kept as an attribute, no launch
         self.action_history = torch.zeros((N, cfg.action_space_dim * 10), device=dev)
-        self.counter = 0
-        self.target_soa = soa(3, N, dev)
-        self.target_position = aos_view(self.target_soa)
-        self.obs_dict = env.get_obs()
-        self.obs_dict["num_obstacles_in_env"] = 1
-        self.terminations = self.obs_dict["crashes"]
-        self.truncations = self.obs_dict["truncations"]
-        self.rewards = torch.zeros(N, device=dev)
         self.prev_position_soa, self.prev_pos_error_soa = soa(3, N, dev), soa(3, N, dev)
         self.prev_position = aos_view(self.prev_position_soa)
         self.prev_pos_error = aos_view(self.prev_pos_error_soa)
-        self.observation_space = Dict({"observations": Box(low=-1.0, high=1.0, shape=(cfg.observation_space_dim,), dtype=np.float32)})
-        self.action_space = Box(low=-1.0, high=1.0, shape=(cfg.action_space_dim,), dtype=np.float32)
-        self.task_obs = {
-            "observations": torch.zeros((N, cfg.observation_space_dim), device=dev),
-            "priviliged_obs": torch.zeros((N, cfg.privileged_observation_space_dim), device=dev),
-            "collisions": torch.zeros((N, 1), device=dev),
-            "rewards": torch.zeros((N, 1), device=dev),
-        }
         # strict_rng: standard normals of the observation noise, [4][N][3] in the reference's draw order (:207-218)
         self.obs_noise = torch.zeros((4, N, 3), device=dev)
-        self.infos = {}
         self._bookkeeping_done = False
         # The reference's step resets every finished env twice: post_reward_calculation_step resets them, then its own
         # reset_idx(reset_envs) calls sim_env.reset_idx again (:180-182) -- a second full set of draws, whose outcome is the
@@ -108,23 +74,9 @@ class PositionSetpointTaskSim2RealEndToEnd(BaseTask):
         # sim_steps) for the same envs, and nothing reads those fields in between.
         env.reset_draw_sets = 2
 
-    def close(self):
-        self.sim_env.delete_env()
-
-    def reset(self):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset()
-        return self.get_return_tuple()
-
     def reset_idx(self, env_ids):
-        self.target_position[:, 0:3] = 0.0
-        self.infos = {}
-        self.sim_env.reset_idx(env_ids)
+        super().reset_idx(env_ids)
         self.action_history[env_ids] = 0.0
-
-    def render(self):
-        return None
 
     def _check_actions(self, actions):
         """The rescaled command goes into the task's own tensor: the caller's is read once and not kept, so a strided one is copied."""
@@ -189,10 +141,6 @@ class PositionSetpointTaskSim2RealEndToEnd(BaseTask):
         )
         self._bookkeeping_done = True
 
-    def get_return_tuple(self):
-        self.process_obs_for_task()
-        return (self.task_obs, self.rewards, self.terminations, self.truncations, self.infos)
-
     def _draw_obs_noise(self):
         """four normal fills of [N, 3], in the reference's order: the torch stream is consumed as there"""
         for k, tag in enumerate(NOISE_TAGS):
@@ -211,9 +159,7 @@ class PositionSetpointTaskSim2RealEndToEnd(BaseTask):
                                             _lib.dptr(self.task_obs["observations"]), env._stream()),
                 "agx_end_to_end_obs",
             )
-        self.task_obs["rewards"] = self.rewards
-        self.task_obs["terminations"] = self.terminations
-        self.task_obs["truncations"] = self.truncations
+        self._publish_step_flags()
 
     def compute_rewards_and_crashes(self, obs_dict):
         """compute_reward, the distance crash, `truncations = sim_steps > episode_len_steps` and the step's reset set"""

@@ -2,7 +2,6 @@
 composite body, the unchanged parameter blocks of every earlier robot, and the numpy restatement the GPU tests compare against
 (tests/end_to_end_ref.py) pinned to the reference's own code through tests/golden/end_to_end_*.npz, tests/golden/end_to_end_cr/
 (tests/golden_gen/gen_golden_end_to_end.py)."""
-import contextlib
 import hashlib
 import json
 import os
@@ -14,43 +13,16 @@ import numpy as np
 import pytest
 import torch
 from conftest import GOLDEN, ROOT
+from task_test_util import config_restored, load_golden
+from task_test_util import same_bits_nan as same
 
 NAME = "position_setpoint_task_sim2real_end_to_end"
+CR = "end_to_end_cr"  # the fixtures made by the reference's code with correctly rounded elementary functions
+CONFIG_KEYS = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps", "return_state_before_reset",
+               "process_actions_for_task")
 FIXTURES = ("end_to_end_reward", "end_to_end_obs", "end_to_end_glue", "end_to_end_config", "step_tinyprop_no_control",
             "step_edge_tinyprop_no_control")
 STEP_CASES = ("tinyprop_no_control", "edge_tinyprop_no_control")
-
-
-def load_golden(name, cr=False):
-    """cr=True: the fixture made by the reference's code with correctly rounded elementary functions (tests/golden/end_to_end_cr/)"""
-    return np.load(os.path.join(GOLDEN, *(["end_to_end_cr"] if cr else []), name + ".npz"))
-
-
-@contextlib.contextmanager
-def config_restored(cfg):
-    """make_task writes its arguments into the (shared) config class: put everything back"""
-    keys = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps", "return_state_before_reset",
-            "process_actions_for_task")
-    old = {k: cfg.__dict__[k] for k in keys}
-    try:
-        yield cfg
-    finally:
-        for k, v in old.items():
-            setattr(cfg, k, v)
-
-
-def bits(a):
-    a = np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32) if a.dtype.kind == "f" else a
-
-
-def same(a, b):
-    """bit for bit, NaN positions equal (a NaN equals a NaN whatever its payload)"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype.kind != "f":
-        return np.array_equal(a, b)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb])
 
 
 def reward_outputs(g):
@@ -92,7 +64,7 @@ def replay_glue(g):
 def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit():
     """every env of every golden: reward and crashes; the observation with the NaN rows at the reference's positions, no row left
     out; every array the reference's real step() produced on the scripted simulator, the second reset_idx call included"""
-    g = load_golden("end_to_end_reward", cr=True)
+    g = load_golden("end_to_end_reward", CR)
     r = reward_outputs(g)
     assert same(r["reward"], g["reward"]) and np.array_equal(r["crashes"], g["crashes_out"].astype(bool))
     dist, prev = r["dist"], np.linalg.norm(g["prev_pos_error"], axis=1)
@@ -101,14 +73,14 @@ def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit():
     assert (dist < prev).sum() > 200 and (dist > prev).sum() > 200 and (dist == prev).sum() > 20
     assert (g["actions"] == np.float32(1.2)).all(axis=1).sum() > 50 and (g["actions"] == np.float32(0.2)).all(axis=1).sum() > 50
     assert g["crashes_in"].sum() > 30 and (g["crashes_out"] & ~g["crashes_in"]).sum() > 100
-    g = load_golden("end_to_end_obs", cr=True)
+    g = load_golden("end_to_end_obs", CR)
     obs = obs_outputs(g)
     assert same(obs, g["obs"])
     a = g["asin_argument"]
     assert (np.abs(a[0:4]) == 1).all() and (np.abs(a[4:8]) == np.nextafter(np.float32(1), np.float32(0))).all()
     assert (np.abs(a[8:12]) == np.nextafter(np.float32(1), np.float32(2))).all() and {-1.0, 1.0} == set(np.sign(a[0:4]))
     assert np.isnan(g["obs"][8:12, 3:9]).all() and not np.isnan(g["obs"][0:8]).any() and np.isnan(g["obs"]).any(axis=1).sum() == (np.abs(a) > 1).sum()
-    g = load_golden("end_to_end_glue", cr=True)
+    g = load_golden("end_to_end_glue", CR)
     out = replay_glue(g)
     for name, v in out.items():
         assert same(v, g[name]), name
@@ -167,7 +139,7 @@ def test_generator_reproduces_the_committed_goldens(cr, tmp_path):
     names = FIXTURES + (() if cr else ("robot_tinyprop",))
     assert sorted(os.listdir(tmp_path)) == sorted(n + ".npz" for n in names)
     for name in names:
-        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, cr=cr)
+        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, CR if cr else None)
         assert sorted(a.files) == sorted(b.files), name
         for key in b.files:
             assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (name, key)
@@ -191,7 +163,7 @@ def test_oracle_on_tinyprop_equals_the_correctly_rounded_reference_bit_for_bit(o
     from aerial_gym_simulator_amd.config.sim_config import BaseSimConfig
     from aerial_gym_simulator_amd.robots.robot_model import robot_params_dict
 
-    g = load_golden("step_" + case, cr=True)
+    g = load_golden("step_" + case, CR)
     pd = json.loads(str(g["params_json"]))
     mine = robot_params_dict(TinyPropCfg, None, "none", BaseSimConfig)
     for key in ("mass", "inertia", "inertia_inv", "wrench_map", "alloc", "min_thrust", "max_thrust", "cq", "use_rps", "integration_rk4",
@@ -362,7 +334,7 @@ def test_task_builds_with_the_reference_attributes():
     from aerial_gym_simulator_amd.task.position_setpoint_task_sim2real_end_to_end import REWARD_CONSTANTS
 
     cfg = ag.task_registry.get_task_config(NAME)
-    with config_restored(cfg):
+    with config_restored(cfg, CONFIG_KEYS):
         cfg.device = "cpu"
         t = ag.task_registry.make_task(NAME, num_envs=8, headless=True)
     assert tuple(t.actions.shape) == tuple(t.prev_actions.shape) == (8, 4) and tuple(t.action_history.shape) == (8, 40)

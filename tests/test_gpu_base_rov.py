@@ -10,45 +10,12 @@ import pytest
 import rov_ref as R
 import torch
 from rov_ref import DERIVED, disturb_of, load_golden, same
+from task_test_util import DEV, NB, derived_of, harness, no_host_sync, npy, split_step, tile
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SIZES = (1, 63, 64, 65, 83, 333)
-NB = 17
 RECORDS = ("step_base_rov_fully_actuated", "step_edge_base_rov_fully_actuated", "step_base_rov_no_control", "step_base_rov_default_fully_actuated")
 SPLIT_GATE = 2e-5  # fused step against the split path, per step (tests/test_gpu_robot_plugin.py)
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
-
-
-def tile(a, n):
-    """the first n rows of the record repeated: env i of the batch is env i % 64 of the fixture"""
-    a = np.asarray(a)
-    return np.ascontiguousarray(a[np.arange(n) % a.shape[0]])
-
-
-def derived_of(H):
-    d = H.get("derived")
-    return dict(euler=d[:, 0:3], qveh=d[:, 3:7], vveh=d[:, 7:10], vbody=d[:, 10:13], wbody=d[:, 13:16])
-
-
-def harness(g, n, k, rov=True):
-    from aerial_gym_simulator_amd import _lib
-    from conftest import golden_params
-    from gpu_harness import DynHarness
-
-    pd = golden_params(g)
-    H = DynHarness(pd, n)
-    H.B.launch_flags = _lib.LAUNCH_ROV if rov else 0
-    H.set(kT=tile(g["kT"], n), tau_inc=tile(g["tau_inc"], n), tau_dec=tile(g["tau_dec"], n), state=tile(g["state"][k], n),
-          thrust=tile(g["thrust_in"][k], n))
-    H.set_gains(*(tile(g[x], n) for x in ("Kp", "Kv", "KR", "Kw")))
-    dist = disturb_of(g, k)
-    if dist is not None:
-        H.set_disturb(tile(dist, n)[None], g["disturb_max"])
-    return H, pd
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -58,7 +25,7 @@ def test_robot_step_equals_the_reference_bit_for_bit(name, n):
     g = load_golden(name, cr=True)
     mask = [int(b) for b in g["application_mask"]]
     for k in range(g["state"].shape[0]):
-        H, _ = harness(g, n, k)
+        H, _ = harness(g, n, k, rov=True)
         F, T = H.robot_step(tile(g["action"][k], n), NB, mask)
         assert same(F, tile(g["force"][k], n)) and same(T, tile(g["torque"][k], n)), (name, k)
         for key, got in derived_of(H).items():
@@ -89,38 +56,6 @@ def test_without_the_flag_the_fixtures_differ():
     assert (derived_of(H)["euler"] != e["euler"][0]).any(axis=1).sum() > 30
 
 
-def split_step(H, pd, action, n):
-    """agx_robot_step -> agx_net_body_wrench -> agx_env_step(AGX_CTRL_WRENCH + AGX_LAUNCH_BODY_WRENCH) with the ROV flag"""
-    import copy
-
-    import aerial_gym_simulator_amd  # noqa: F401
-    from aerial_gym_simulator_amd import _lib
-    from aerial_gym_simulator_amd.config.robot_config import BaseROVCfg
-    from aerial_gym_simulator_amd.robots.robot_model import link_frames
-
-    mask = list(BaseROVCfg.control_allocator_config.application_mask)
-    a = torch.from_numpy(np.ascontiguousarray(action, np.float32)).to(DEV)
-    Fd, Td = torch.zeros(n, NB, 3, device=DEV), torch.zeros(n, NB, 3, device=DEV)
-    args = _lib.AgxRobotStepArgs()
-    args.force, args.torque, args.num_bodies, args.substep = _lib.dptr(Fd), _lib.dptr(Td), NB, 0
-    for j, b in enumerate(mask):
-        args.body_of_motor[j] = int(b)
-    _lib.check(H.lib.agx_robot_step(H.P, H.B, n, _lib.dptr(a), C.byref(args), H.stream()), "agx_robot_step")
-    L, known = link_frames(BaseROVCfg, NB)
-    assert [b for b, k in enumerate(known) if k] == [0] + mask
-    net = torch.zeros(n, 6, device=DEV)
-    _lib.check(H.lib.agx_net_body_wrench(n, C.byref(L), _lib.dptr(Fd), _lib.dptr(Td), _lib.dptr(net), H.stream()), "agx_net_body_wrench")
-    P = copy.copy(H.P)
-    P.controller = _lib.CTRL_IDS["wrench"]
-    flags = H.B.launch_flags
-    H.B.launch_flags = flags | _lib.LAUNCH_BODY_WRENCH
-    try:
-        _lib.check(H.lib.agx_env_step(P, H.B, n, _lib.dptr(net), 1, None, H.stream()), "agx_env_step")
-    finally:
-        H.B.launch_flags = flags
-    torch.cuda.synchronize()
-
-
 @pytest.mark.parametrize("n", SIZES)
 @pytest.mark.parametrize("name", ("step_base_rov_fully_actuated", "step_edge_base_rov_fully_actuated", "step_base_rov_no_control"))
 def test_fused_env_step_equals_the_split_path(name, n):
@@ -129,17 +64,18 @@ def test_fused_env_step_equals_the_split_path(name, n):
     within 2e-5 absolute (the wrench map folded ahead of time against the per-body sum).  Measured on an MI355X: at most 2.4e-7 on
     the nominal records, 7.6e-6 on the edge record (one ulp of the 100 m/s rows)"""
     from aerial_gym_simulator_amd import _lib
+    from aerial_gym_simulator_amd.config.robot_config import BaseROVCfg
 
     g = load_golden(name, cr=True)
     for k in range(g["state"].shape[0]):
         a = tile(g["action"][k], n)
-        Hf, pd = harness(g, n, k)
+        Hf, _ = harness(g, n, k, rov=True)
         buf = C.create_string_buffer(128)
         assert Hf.lib.agx_env_step_kernel(Hf.P, Hf.B, n, 1, None, buf, 128) == 0
         assert buf.value.decode().startswith("k_env_step_rov<%d,true,true>_" % _lib.CTRL_IDS["none" if "no_control" in name else "fully_actuated"]), buf.value
         Hf.substeps(a, 1)
-        Hs, _ = harness(g, n, k)
-        split_step(Hs, pd, a, n)
+        Hs, _ = harness(g, n, k, rov=True)
+        split_step(Hs, BaseROVCfg, a, n)
         assert same(Hf.get("thrust"), Hs.get("thrust")) and same(Hf.get("thrust"), tile(g["thrust_out"][k], n))
         for key, got in derived_of(Hf).items():
             assert same(got, tile(g[key][k], n)) and same(got, derived_of(Hs)[key]), (name, k, key)
@@ -155,7 +91,7 @@ def test_fused_env_step_equals_the_oracle_where_the_drag_laws_coincide(orc, n):
     for name in ("step_base_rov_default_fully_actuated", "step_edge_base_rov_fully_actuated"):
         g = load_golden(name, cr=True)
         for k in range(g["state"].shape[0]):
-            H, pd = harness(g, n, k)
+            H, pd = harness(g, n, k, rov=True)
             H.substeps(tile(g["action"][k], n), 1)
             st, th = tile(g["state"][k], n).copy(), tile(g["thrust_in"][k], n).copy()
             dist = disturb_of(g, k)
@@ -274,7 +210,7 @@ def test_fused_two_sub_steps_equal_the_oracle(orc, n):
     law coincides: state and thrusts bit for bit after both sub-steps, the derived tensors those of the second sub-step's
     pre-physics state with the Euler angles of the restatement"""
     g = load_golden("step_base_rov_default_fully_actuated", cr=True)
-    H, pd = harness(g, n, 0)
+    H, pd = harness(g, n, 0, rov=True)
     buf = C.create_string_buffer(128)
     assert H.lib.agx_env_step_kernel(H.P, H.B, n, 2, None, buf, 128) == 0 and buf.value.decode().startswith("k_env_step_rov<7,false,true>_")
     a = tile(g["action"][0], n)
@@ -306,7 +242,7 @@ def test_other_reset_entry_points_refuse_the_flag():
 
     n = 8
     g = load_golden("step_base_rov_default_fully_actuated", cr=True)
-    H, _ = harness(g, n, 0)
+    H, _ = harness(g, n, 0, rov=True)
     Rr = AgxResetArgs()
     z = torch.zeros(n, 16, device=DEV)
     A = _lib.AgxNavRobotSideArgs()
@@ -345,7 +281,7 @@ def test_launchers_refuse_the_flag_for_other_robots():
                            dict(tau_inc=(0.01, 0.02), tau_dec=(0.01, 0.02), kT=(1e-5, 2e-5)), np.zeros(13), np.zeros(13), ([-1] * 3, [-1] * 3, [1] * 3, [1] * 3))
         assert not np.isnan(H.get("state")).any()
     g = load_golden("step_base_rov_fully_actuated", cr=True)
-    H, _ = harness(g, 8, 0)
+    H, _ = harness(g, 8, 0, rov=True)
     H.B.launch_flags = _lib.LAUNCH_ROV | 0x20000
     with pytest.raises(RuntimeError, match="launch_flags"):
         H.substeps(g["action"][0][:8], 1)
@@ -475,27 +411,6 @@ def test_strict_trace_equals_the_oracle_and_consumes_the_reference_draws(orc):
         steps = npy(env.sim_steps)
         assert (steps[want_mask] == 0).all() and (steps[~want_mask] > 0).all()
     assert resets == 5 and np.isfinite(npy(g["robot_state_tensor"])).all()
-
-
-class no_host_sync:
-    """every host synchronisation torch offers is an error inside this block"""
-
-    NAMES = ("item", "cpu", "tolist", "nonzero", "numpy", "__bool__", "__int__", "__float__")
-
-    def __enter__(self):
-        def refuse(*a, **k):
-            raise AssertionError("host synchronisation inside a default-mode step")
-
-        self.saved = {name: getattr(torch.Tensor, name) for name in self.NAMES}
-        self.sync = torch.cuda.synchronize
-        for name in self.NAMES:
-            setattr(torch.Tensor, name, refuse)
-        torch.cuda.synchronize = refuse
-
-    def __exit__(self, *exc):
-        for name, fn in self.saved.items():
-            setattr(torch.Tensor, name, fn)
-        torch.cuda.synchronize = self.sync
 
 
 TRACE_STEPS, TRACE_N = 20, 65

@@ -18,6 +18,7 @@ import torch
 import collision_cases as cc
 from aerial_gym_simulator_amd import _lib
 from gpu_harness import CTRL_KEY, DynHarness
+from task_test_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -66,10 +67,6 @@ def expected_kernel(pd, quad, k, n):
     if quad:
         return f"k_env_step_quad_loop<{pd['num_motors']},{ctrl}>_"
     return f"k_env_step<{pd['num_motors']},{ctrl},{'true' if k == 1 else 'false'},{'true' if n <= 65536 else 'false'}>_"
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def harness_for(fam, quad):

@@ -2,62 +2,21 @@
 C ABI and through EnvManager, against the restatement of its two pieces on top of the oracle (tests/com_offset_ref.py, pinned by
 tests/test_com_offset.py) and against agx_env_step where the two must coincide."""
 import copy
-import ctypes as C
 import json
 
 import com_offset_ref as CR
 import numpy as np
 import pytest
 import torch
-from rov_ref import disturb_of, same
+from rov_ref import same
+from task_test_util import DEV, derived_of, harness, no_host_sync, npy, split_step, tile
+from task_test_util import com_offset as offset
 from test_com_offset import RECORDS, load
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SIZES = (1, 64, 65, 83)
-NB = 17
 SPLIT_GATE = 2e-5  # fused step against the split path, per step (tests/test_gpu_robot_plugin.py)
 GAINS = ("kT", "tau_inc", "tau_dec", "Kp", "Kv", "KR", "Kw")
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
-
-
-def tile(a, n):
-    """the first n rows of the record repeated: env i of the batch is env i % 64 of the fixture"""
-    a = np.asarray(a)
-    return np.ascontiguousarray(a[np.arange(n) % a.shape[0]])
-
-
-def derived_of(H):
-    d = H.get("derived")
-    return dict(euler=d[:, 0:3], qveh=d[:, 3:7], vveh=d[:, 7:10], vbody=d[:, 10:13], wbody=d[:, 13:16])
-
-
-def harness(g, n, k, pd=None, dist=None):
-    """a DynHarness on sub-step k of the record g; dist [K, n, 7]: the host draws of the launch (default: row k of the record)"""
-    from gpu_harness import DynHarness
-
-    pd = pd or json.loads(str(g["params_json"]))
-    H = DynHarness(pd, n)
-    H.set(kT=tile(g["kT"], n), tau_inc=tile(g["tau_inc"], n), tau_dec=tile(g["tau_dec"], n), state=tile(g["state"][k], n),
-          thrust=tile(g["thrust_in"][k], n))
-    H.set_gains(*(tile(g[x], n) for x in ("Kp", "Kv", "KR", "Kw")))
-    if dist is None and disturb_of(g, k) is not None:
-        dist = tile(disturb_of(g, k), n)[None]
-    if dist is not None:
-        H.set_disturb(dist, g["disturb_max"])
-    return H, pd
-
-
-def offset(c):
-    from aerial_gym_simulator_amd import _lib
-
-    off = _lib.AgxComOffset()
-    for i in range(3):
-        off.c[i] = float(c[i])
-    return off
 
 
 def step_com(H, action, k, c, P=None):
@@ -147,44 +106,14 @@ def test_zero_offset_through_the_new_entry_equals_agx_env_step(name):
     assert np.isfinite(outs[0]["state"]).all()
 
 
-def split_step(H, pd, action, n, c, substep=0):
-    """agx_robot_step -> agx_net_body_wrench (poses about the centre of mass) -> agx_env_step_com(AGX_CTRL_WRENCH + AGX_LAUNCH_BODY_WRENCH)"""
-    import aerial_gym_simulator_amd  # noqa: F401
-    from aerial_gym_simulator_amd import _lib
-    from aerial_gym_simulator_amd.config.robot_config import BaseRandCfg
-    from aerial_gym_simulator_amd.robots.robot_model import link_frames
-
-    mask = list(BaseRandCfg.control_allocator_config.application_mask)
-    a = torch.from_numpy(np.ascontiguousarray(action, np.float32)).to(DEV)
-    Fd, Td = torch.zeros(n, NB, 3, device=DEV), torch.zeros(n, NB, 3, device=DEV)
-    args = _lib.AgxRobotStepArgs()
-    args.force, args.torque, args.num_bodies, args.substep = _lib.dptr(Fd), _lib.dptr(Td), NB, substep
-    for j, b in enumerate(mask):
-        args.body_of_motor[j] = int(b)
-    _lib.check(H.lib.agx_robot_step(H.P, H.B, n, _lib.dptr(a), C.byref(args), H.stream()), "agx_robot_step")
-    L, known = link_frames(BaseRandCfg, NB)
-    assert [b for b, k in enumerate(known) if k] == [0] + mask
-    assert same(np.float32([L.pos[0][i] for i in range(3)]), -c)  # the root body sits at -c from the mass centre
-    net = torch.zeros(n, 6, device=DEV)
-    _lib.check(H.lib.agx_net_body_wrench(n, C.byref(L), _lib.dptr(Fd), _lib.dptr(Td), _lib.dptr(net), H.stream()), "agx_net_body_wrench")
-    P = copy.copy(H.P)
-    P.controller = _lib.CTRL_IDS["wrench"]
-    flags = H.B.launch_flags
-    H.B.launch_flags = flags | _lib.LAUNCH_BODY_WRENCH
-    try:
-        _lib.check(H.lib.agx_env_step_com(P, H.B, n, _lib.dptr(net), 1, None, offset(c), H.stream()), "agx_env_step_com")
-    finally:
-        H.B.launch_flags = flags
-    torch.cuda.synchronize()
-    return npy(net)
-
-
 @pytest.mark.parametrize("name", ("step_base_random_position", "step_base_random_no_control"))
 def test_fused_step_equals_the_split_path(orc, name):
     """base_random, 83 envs, 3 steps: the one fused launch against robot step -> net body wrench about the centre of mass ->
     integration with AGX_CTRL_WRENCH; thrusts and derived tensors bit for bit, the state within 2e-5 absolute per step (the wrench
     map folded ahead of time against the per-body sum; the root body's lever arm as cross(F_root, c) against r x F with r = -c).
     The integrating launch alone equals the restatement bit for bit.  Measured on an MI355X: at most 1.4e-6."""
+    from aerial_gym_simulator_amd.config.robot_config import BaseRandCfg
+
     n = 83
     g = load(name, cr=True)
     pd = json.loads(str(g["params_json"]))
@@ -203,7 +132,7 @@ def test_fused_step_equals_the_split_path(orc, name):
             hs.append(H)
         Hf, Hs = hs
         step_com(Hf, a, 1, c)
-        net = split_step(Hs, pd, a, n, c)
+        net = split_step(Hs, BaseRandCfg, a, n, c)
         want = st.copy()
         CR.body_wrench_substep(orc, P, want, net, c)
         assert same(Hs.get("state"), want), t
@@ -297,27 +226,6 @@ def test_entry_refuses_what_it_does_not_carry():
 
 
 # ---- through EnvManager and the task -----------------------------------------------------------------------------------------
-class no_host_sync:
-    """every host synchronisation torch offers is an error inside this block"""
-
-    NAMES = ("item", "cpu", "tolist", "nonzero", "numpy", "__bool__", "__int__", "__float__")
-
-    def __enter__(self):
-        def refuse(*a, **k):
-            raise AssertionError("host synchronisation inside a default-mode step")
-
-        self.saved = {name: getattr(torch.Tensor, name) for name in self.NAMES}
-        self.sync = torch.cuda.synchronize
-        for name in self.NAMES:
-            setattr(torch.Tensor, name, refuse)
-        torch.cuda.synchronize = refuse
-
-    def __exit__(self, *exc):
-        for name, fn in self.saved.items():
-            setattr(torch.Tensor, name, fn)
-        torch.cuda.synchronize = self.sync
-
-
 def task_trace(robot_name, monkeypatch, steps=20, n=64):
     """position_setpoint_task with this robot under lee_position_control, device generator: `steps` task steps under the no-sync
     guard, truncations written on the device every fifth step -> (library calls per step, task, states after every step)"""

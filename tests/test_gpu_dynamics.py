@@ -496,3 +496,33 @@ def test_four_lanes_per_env_kernels_cover_the_six_lee_laws(case, k, monkeypatch)
     for s, (a, b) in enumerate(zip(outs["0"], outs["1"])):
         for name, x, y in zip(("state", "thrust", "derived", "wrench"), a, b):
             assert np.array_equal(x, y), (case, k, s, name, np.abs(x - y).max())
+
+
+@pytest.mark.parametrize("pattern", ["none", "one", "all", "random"])
+@pytest.mark.parametrize("parity", [0, 1])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])  # one lane, a partial wave, the exact wave, one over, a partial second 256-thread workgroup
+def test_reset_set_entry_at_wave_edges(n, parity, pattern):
+    """agx_reset_set through the C ABI, with and without reset_on_collision: reset_mask = crashes * reset_on_collision | truncations
+    for every env (the mask starts at 7: a lane that was not written shows), the flag word of this parity = some env resets, the
+    other parity's word and the two inputs unchanged.  `one`: a single crashed env, the last one (the last, partial wave)."""
+    from task_test_util import Buffers, host
+
+    crashes, trunc = np.zeros(n, bool), np.zeros(n, bool)
+    if pattern == "one":
+        crashes[n - 1] = True
+    elif pattern == "all":
+        crashes[:], trunc[:] = True, True
+    elif pattern == "random":
+        rng = np.random.default_rng(1000 * n + parity)
+        crashes, trunc = rng.random(n) < 0.3, rng.random(n) < 0.2
+    for roc in (0, 1):
+        H = Buffers(n, np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), crashes=crashes, parity=parity)
+        H.truncations.copy_(torch.from_numpy(trunc))
+        H.reset_flag[parity ^ 1] = 5
+        _agx_lib.check(H.lib.agx_reset_set(H.B, n, roc, H.stream()), "agx_reset_set")
+        torch.cuda.synchronize()
+        mask = (crashes & bool(roc)) | trunc
+        assert np.array_equal(host(H.reset_mask), mask.astype(np.uint8)), (roc, np.flatnonzero(host(H.reset_mask) != mask))
+        flags = host(H.reset_flag)
+        assert flags[parity] == int(mask.any()) and flags[parity ^ 1] == 5, (roc, flags)
+        assert np.array_equal(host(H.crashes), crashes) and np.array_equal(host(H.truncations), trunc)

@@ -3,96 +3,21 @@ numbers (tests/golden/end_to_end_cr/*.npz) and the restatement tests/end_to_end_
 tests/test_end_to_end_task.py), bit for bit; agx_post_step_end_to_end against the composition of the launches it replaces; the
 device generator's noise; tinyprop's dynamics (the first airframe with products of inertia) against the oracle; the task through the
 Task API, default and strict_rng."""
-import contextlib
 import copy
-import os
 
 import end_to_end_ref as R
 import numpy as np
 import pytest
 import torch
-from conftest import GOLDEN
+from task_test_util import DEV, Buffers, RecordingSource, config_restored, dev, host, load_golden, offset_consumed_by, rows, soa
+from task_test_util import same_bits_nan as same
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+CR = "end_to_end_cr"  # the fixtures made by the reference's code with correctly rounded elementary functions
+CONFIG_KEYS = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps", "return_state_before_reset", "crash_dist",
+               "process_actions_for_task")
 NAME = "position_setpoint_task_sim2real_end_to_end"
 SIZES = (1, 63, 64, 65, 83, 333)  # one lane, a partial wave, the exact wave, one over, a partial second block, more than five blocks
-
-
-def load_golden(name, cr=True):
-    return np.load(os.path.join(GOLDEN, *(["end_to_end_cr"] if cr else []), name + ".npz"))
-
-
-@contextlib.contextmanager
-def config_restored(cfg):
-    """make_task writes its arguments into the (shared) config class: put everything back"""
-    keys = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps", "return_state_before_reset", "crash_dist",
-            "process_actions_for_task")
-    old = {k: cfg.__dict__[k] for k in keys}
-    try:
-        yield cfg
-    finally:
-        for k, v in old.items():
-            setattr(cfg, k, v)
-
-
-def bits(a):
-    a = np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32) if a.dtype.kind == "f" else a
-
-
-def same(a, b):
-    """bit for bit, NaN positions equal"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype.kind != "f":
-        return np.array_equal(a, b)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb])
-
-
-def dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype=dtype).contiguous()
-
-
-def soa(a):
-    return dev(np.ascontiguousarray(np.asarray(a, np.float32).T))
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def rows(a, n):
-    """golden rows sliced to n (wrapping round where the golden has fewer)"""
-    a = np.asarray(a)
-    return a[np.arange(n) % a.shape[0]].copy()
-
-
-class Buffers:
-    """AgxEnvBuffers over tensors made from reference-layout arrays"""
-
-    def __init__(self, n, position, orientation, linvel=None, body_angvel=None, crashes=None, sim_steps=None, parity=1):
-        from aerial_gym_simulator_amd import _lib
-
-        self.lib, self._lib, self.n = _lib.load(), _lib, n
-        z = lambda c: np.zeros((n, c), np.float32)  # noqa: E731
-        state = np.concatenate([position, orientation, linvel if linvel is not None else z(3), z(3)], axis=1)
-        derived = np.concatenate([z(13), body_angvel if body_angvel is not None else z(3)], axis=1)
-        self.state, self.derived = soa(state), soa(derived)
-        self.crashes = dev(np.asarray(crashes if crashes is not None else np.zeros(n, bool)).astype(bool))
-        self.truncations = torch.zeros(n, dtype=torch.bool, device=DEV)
-        self.sim_steps = dev(np.asarray(sim_steps if sim_steps is not None else np.zeros(n), np.int32))
-        self.reset_mask = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
-        self.reset_flag = torch.zeros(2, dtype=torch.int32, device=DEV)
-        B = _lib.AgxEnvBuffers()
-        p = _lib.dptr
-        B.state, B.derived = p(self.state), p(self.derived)
-        B.crashes, B.truncations, B.sim_steps = p(self.crashes), p(self.truncations), p(self.sim_steps)
-        B.reset_mask, B.reset_flag, B.flag_parity = p(self.reset_mask), p(self.reset_flag), parity
-        self.B, self.parity = B, parity
-
-    def stream(self):
-        return self._lib.current_stream(DEV)
 
 
 def reward_constants():
@@ -104,7 +29,7 @@ def reward_constants():
 @pytest.mark.parametrize("n", SIZES)
 def test_pre_step_kernel_equals_the_restatement_bit_for_bit(n):
     """the rescale on the glue fixture's actions (beyond +-1 among them) plus a NaN, -0.0 and the exact limits; prev_position"""
-    g = load_golden("end_to_end_glue")
+    g = load_golden("end_to_end_glue", CR)
     a = rows(g["action_in"].reshape(-1, 4), n)
     a[0] = [np.nan, -0.0, 1.0, -1.0]
     pos = rows(g["pre_position"].reshape(-1, 3), n)
@@ -124,11 +49,11 @@ def test_pre_step_kernel_equals_the_restatement_bit_for_bit(n):
 
 @pytest.mark.parametrize("n", SIZES)
 def test_reward_kernel_equals_the_reference_bit_for_bit(n):
-    g = load_golden("end_to_end_reward")
+    g = load_golden("end_to_end_reward", CR)
     G = lambda name: rows(g[name], n)  # noqa: E731
     episode_len = 4
     sim_steps = (np.arange(n) * 3) % 9
-    H = Buffers(n, G("position"), G("orientation"), G("linvel"), G("body_angvel"), crashes=G("crashes_in"), sim_steps=sim_steps)
+    H = Buffers(n, G("position"), G("orientation"), linvel=G("linvel"), body_angvel=G("body_angvel"), crashes=G("crashes_in"), sim_steps=sim_steps)
     p = H._lib.dptr
     target, act, pact, ppe = soa(G("target")), dev(G("actions")), dev(G("prev_actions")), soa(G("prev_pos_error"))
     rew = torch.zeros(n, device=DEV)
@@ -151,10 +76,10 @@ def test_reward_kernel_equals_the_reference_bit_for_bit(n):
 @pytest.mark.parametrize("parity", [0, 1])
 @pytest.mark.parametrize("reset_on_collision", [0, 1])
 def test_reward_kernel_on_both_flag_parities_with_and_without_reset_on_collision(parity, reset_on_collision):
-    g = load_golden("end_to_end_reward")
+    g = load_golden("end_to_end_reward", CR)
     n = 65
     G = lambda name: rows(g[name], n)  # noqa: E731
-    H = Buffers(n, G("position"), G("orientation"), G("linvel"), G("body_angvel"), crashes=G("crashes_in"), parity=parity)
+    H = Buffers(n, G("position"), G("orientation"), linvel=G("linvel"), body_angvel=G("body_angvel"), crashes=G("crashes_in"), parity=parity)
     p = H._lib.dptr
     target, act, pact, ppe = soa(G("target")), dev(G("actions")), dev(G("prev_actions")), soa(G("prev_pos_error"))
     rew = torch.zeros(n, device=DEV)
@@ -172,10 +97,10 @@ def test_reward_kernel_on_both_flag_parities_with_and_without_reset_on_collision
 @pytest.mark.parametrize("n", SIZES)
 def test_obs_kernel_with_host_noise_equals_the_reference_bit_for_bit(n):
     """the NaN rows included (n >= 12: one ulp outside +-1 gives NaN at the reference's positions)"""
-    g = load_golden("end_to_end_obs")
+    g = load_golden("end_to_end_obs", CR)
     G = lambda name: rows(g[name], n)  # noqa: E731
     s = G("state")
-    H = Buffers(n, s[:, 0:3], s[:, 3:7], s[:, 7:10], G("body_angvel"))
+    H = Buffers(n, s[:, 0:3], s[:, 3:7], linvel=s[:, 7:10], body_angvel=G("body_angvel"))
     p = H._lib.dptr
     z = dev(np.stack([rows(g["z"][j], n) for j in range(4)]))
     target = soa(G("target"))
@@ -201,11 +126,11 @@ def device_normals(lib_mod, lib, B, n):
 
 
 def test_device_noise_is_a_pure_function_of_seed_global_env_and_step():
-    g = load_golden("end_to_end_obs")
+    g = load_golden("end_to_end_obs", CR)
     z = {}
     for n, base, step, seed in ((83, 0, 5, 1234), (333, 0, 5, 1234), (33, 50, 5, 1234), (83, 0, 6, 1234), (83, 0, 5, 1235)):
         s = rows(g["state"], n)
-        H = Buffers(n, s[:, 0:3], s[:, 3:7], s[:, 7:10], rows(g["body_angvel"], n))
+        H = Buffers(n, s[:, 0:3], s[:, 3:7], linvel=s[:, 7:10], body_angvel=rows(g["body_angvel"], n))
         H.B.rng_seed, H.B.env_index_base, H.B.step_counter = seed, base, step
         z[(n, base, step, seed)] = device_normals(H._lib, H.lib, H.B, n)
         if n == 83 and step == 5 and seed == 1234:  # the observation with the device generator == with those normals handed in
@@ -275,7 +200,7 @@ def test_post_step_equals_the_composition_of_the_launches_it_replaces(mask_kind,
     from aerial_gym_simulator_amd import _lib
     from aerial_gym_simulator_amd.registry.task_registry import task_registry
 
-    with config_restored(task_registry.get_task_config(NAME)):
+    with config_restored(task_registry.get_task_config(NAME), CONFIG_KEYS):
         task = make_task(n)
         env, g = task.sim_env, task.obs_dict
         mm = env.robot_manager.robot.control_allocator.motor_model
@@ -408,7 +333,7 @@ def test_tinyprop_dynamics_substep_equals_the_oracle_bit_for_bit(orc):
     _, bad = run(mutant)
     assert not same(bad[0][0], got[0][0]) and not same(bad[1][0], st)
     for case in ("step_tinyprop_no_control", "step_edge_tinyprop_no_control"):
-        g = load_golden(case)
+        g = load_golden(case, CR)
         H = DynHarness(pd, n)
         H.set(kT=rows(g["kT"], n), tau_inc=rows(g["tau_inc"], n), tau_dec=rows(g["tau_dec"], n))
         K = g["state"].shape[0]
@@ -429,53 +354,6 @@ def ctypes_kernel_name(_lib, H):
     buf = ctypes.create_string_buffer(128)
     _lib.check(H.lib.agx_env_step_kernel(H.P, H.B, H.n, 1, None, buf, 128), "agx_env_step_kernel")
     return buf.value.decode()
-
-
-class RecordingSource:
-    """the env's random source, passing every call through to torch and keeping what the normal fills returned"""
-
-    def __init__(self, device):
-        from aerial_gym_simulator_amd.utils.random_source import TorchRandomSource
-
-        self.inner = TorchRandomSource(device)
-        self.normals, self.calls = [], []
-
-    def rand(self, *shape, tag=""):
-        self.calls.append(("rand", tuple(shape), tag))
-        return self.inner.rand(*shape, tag=tag)
-
-    def rand_into(self, out, tag=""):
-        self.calls.append(("rand", tuple(out.shape), tag))
-        return self.inner.rand_into(out, tag=tag)
-
-    def bernoulli(self, p, *shape, tag=""):
-        self.calls.append(("bernoulli", tuple(shape), tag))
-        return self.inner.bernoulli(p, *shape, tag=tag)
-
-    def normal_into(self, out, tag=""):
-        self.calls.append(("normal", tuple(out.shape), tag))
-        r = self.inner.normal_into(out, tag=tag)
-        self.normals.append(out.detach().clone())
-        return r
-
-    def gauss(self, mean, std):
-        return self.inner.gauss(mean, std)
-
-
-def offset_consumed_by(calls):
-    """how far the listed fills move the default generator's offset (on a saved and restored generator state)"""
-    gen = torch.cuda.default_generators[0]
-    state = gen.get_state()
-    try:
-        start = gen.get_offset()
-        for what, shape, _ in calls:
-            if what == "normal":
-                torch.empty(shape, device=DEV).normal_()
-            else:
-                torch.empty(shape, device=DEV).uniform_()
-        return gen.get_offset() - start
-    finally:
-        gen.set_state(state)
 
 
 def reference_call_list(n, resets):
@@ -499,7 +377,7 @@ def test_task_trace_equals_the_restatement_on_the_dict_tensors(strict):
 
     n, steps, episode_len, crash_dist = 83, 40, 12, 6.0
     rs = RecordingSource(DEV)
-    with config_restored(task_registry.get_task_config(NAME)):
+    with config_restored(task_registry.get_task_config(NAME), CONFIG_KEYS):
         task = make_task(n, strict=strict, args={"random_source": rs}, episode_len_steps=episode_len, crash_dist=crash_dist)
         env, d = task.sim_env, task.obs_dict
         launches = []
@@ -615,7 +493,7 @@ def test_general_path_state_before_reset_explicit_reset_and_a_user_rescale():
         calls.append(tuple(actions.shape))
         return torch.clamp(actions, -1, 1) * 0.25 + 0.75
 
-    with config_restored(task_registry.get_task_config(NAME)) as cfg:
+    with config_restored(task_registry.get_task_config(NAME), CONFIG_KEYS) as cfg:
         task = make_task(n, return_state_before_reset=True, episode_len_steps=3, crash_dist=50.0)
         env, d = task.sim_env, task.obs_dict
         launches = []
@@ -658,7 +536,7 @@ def test_make_task_through_the_alias_steps_with_finite_outputs():
     from aerial_gym.config.task_config.position_setpoint_task_sim2real_end_to_end_config import task_config
     from aerial_gym.registry.task_registry import task_registry
 
-    with config_restored(task_config):
+    with config_restored(task_config, CONFIG_KEYS):
         task = task_registry.make_task(NAME, num_envs=64)
         assert task.action_limit_max.device.type == "cuda" and task_config.action_limit_max.device.type == "cpu"
         obs = task.reset()[0]
@@ -689,7 +567,7 @@ def test_hover_thrust_holds_a_level_tinyprop():
     from aerial_gym_simulator_amd.registry.task_registry import task_registry
 
     n = 64
-    with config_restored(task_registry.get_task_config(NAME)):
+    with config_restored(task_registry.get_task_config(NAME), CONFIG_KEYS):
         task = make_task(n, crash_dist=1000.0)
         env, d = task.sim_env, task.obs_dict
         task.reset()

@@ -15,13 +15,10 @@ import time
 import numpy as np
 import pytest
 import torch
+from task_test_util import npy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
 
 
 def test_config1_every_env_of_8192_for_50_steps(orc):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 from conftest import max_abs, max_rel, rel_err
+from task_test_util import npy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -45,10 +46,6 @@ class RecordingSource:
 
     def last(self, tag):
         return self.log[tag][-1].cpu().numpy()
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
 
 
 NAV_CASES = {

@@ -2,14 +2,13 @@
 (a numpy restatement pinned to the reference's own code on the CPU by tests/test_radar_navigation_task.py): every kernel result is
 compared with it bit for bit, and with the plain-torch goldens within the bounds of tests/test_gpu_lidar_nav.py."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import radar_ref as R
 import torch
-from conftest import GOLDEN, golden_params, rel_err
-from conftest import load_golden as load_common
+from conftest import golden_params, rel_err
+from task_test_util import host, load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -17,22 +16,14 @@ NAME = "radar_navigation_task"
 F = np.float32
 
 
-def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
-
-
 def T(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def _harness(n):
     from gpu_harness import DynHarness
 
-    return DynHarness(golden_params(load_common("step_quad_velocity")), n)
+    return DynHarness(golden_params(load_golden("step_quad_velocity")), n)
 
 
 class ImageRun:

@@ -8,15 +8,12 @@ oracle's restatement of the same path (orc.robot_step -> orc.net_body_wrench -> 
 import numpy as np
 import pytest
 import torch
+from task_test_util import npy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 EXTRA_F = np.array([0.3, -0.2, 0.5], np.float32)  # constant extra force on the root body, in its frame [N]
 EXTRA_TZ = np.float32(0.01)                       # and a torque about the z axis of the third motor link [N m]
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
 
 
 def _register(name, cfg_name, with_extra):

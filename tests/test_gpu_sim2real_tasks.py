@@ -2,104 +2,32 @@
 numbers (tests/golden/sim2real_cr/*.npz, bit for bit), the tasks through the Task API against tests/sim2real_ref.py applied to
 snapshots of the dict tensors (bit for bit; that restatement is pinned to the reference by tests/test_sim2real_tasks.py), and
 the two actors the reference trained flying task.step() on the task's own noisy observations."""
-import contextlib
 import os
 
 import numpy as np
 import pytest
 import sim2real_ref as R
 import torch
-from conftest import GOLDEN
+from task_test_util import DEV, Buffers, RecordingSource, config_restored, dev, host, load_golden, offset_consumed_by, rows, soa
+from task_test_util import same_bits as same
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+CR = "sim2real_cr"  # the fixtures made by the reference's code with correctly rounded elementary functions
+CONFIG_KEYS = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps")
 KINDS = (("velocity", R.VELOCITY), ("acceleration", R.ACCELERATION))
 NAMES = {"velocity": "position_setpoint_task_sim2real", "acceleration": "position_setpoint_task_acceleration_sim2real"}
 SIZES = (1, 63, 64, 65, 257)  # a partial wave, the exact wave, one over, more than four waves
 
 
-def load_golden(name, cr=False):
-    """cr=True: the fixture made by the reference's code with correctly rounded elementary functions (tests/golden/sim2real_cr/)"""
-    return np.load(os.path.join(GOLDEN, *(["sim2real_cr"] if cr else []), name + ".npz"))
-
-
-@contextlib.contextmanager
-def config_restored(cfg):
-    """make_task writes its arguments into the (shared) config class: put everything back"""
-    keys = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps")
-    old = {k: getattr(cfg, k) for k in keys}
-    try:
-        yield cfg
-    finally:
-        for k, v in old.items():
-            setattr(cfg, k, v)
-
-
-def bits(a):
-    a = np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32) if a.dtype.kind == "f" else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype=dtype).contiguous()
-
-
-def soa(a):
-    return dev(np.ascontiguousarray(np.asarray(a, np.float32).T))
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def rows(a, n):
-    """golden rows sliced to n (wrapping round where the golden has fewer)"""
-    a = np.asarray(a)
-    return a[np.arange(n) % a.shape[0]].copy()
-
-
-class Buffers:
-    """AgxEnvBuffers over tensors made from reference-layout arrays"""
-
-    def __init__(self, n, position, orientation, vehicle_orientation=None, body_linvel=None, body_angvel=None, robot_actions=None,
-                 crashes=None, sim_steps=None, parity=1):
-        from aerial_gym_simulator_amd import _lib
-
-        self.lib, self._lib, self.n = _lib.load(), _lib, n
-        z = lambda c: np.zeros((n, c), np.float32)  # noqa: E731
-        state = np.concatenate([position, orientation, z(6)], axis=1)
-        derived = np.concatenate([z(3), vehicle_orientation if vehicle_orientation is not None else z(4), z(3),
-                                  body_linvel if body_linvel is not None else z(3), body_angvel if body_angvel is not None else z(3)], axis=1)
-        self.state, self.derived = soa(state), soa(derived)
-        self.actions = soa(robot_actions if robot_actions is not None else z(4))
-        self.crashes = dev(np.asarray(crashes if crashes is not None else np.zeros(n, bool)).astype(bool))
-        self.truncations = torch.zeros(n, dtype=torch.bool, device=DEV)
-        self.sim_steps = dev(np.asarray(sim_steps if sim_steps is not None else np.zeros(n), np.int32))
-        self.reset_mask = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
-        self.reset_flag = torch.zeros(2, dtype=torch.int32, device=DEV)
-        B = _lib.AgxEnvBuffers()
-        p = _lib.dptr
-        B.state, B.derived, B.actions = p(self.state), p(self.derived), p(self.actions)
-        B.crashes, B.truncations, B.sim_steps = p(self.crashes), p(self.truncations), p(self.sim_steps)
-        B.reset_mask, B.reset_flag, B.flag_parity = p(self.reset_mask), p(self.reset_flag), parity
-        self.B, self.parity = B, parity
-
-    def stream(self):
-        return self._lib.current_stream(DEV)
-
-
 @pytest.mark.parametrize("n", SIZES)
 @pytest.mark.parametrize("kind,k", KINDS)
 def test_reward_kernel_equals_the_reference_bit_for_bit(kind, k, n):
-    g = load_golden("sim2real_reward", cr=True)
+    g = load_golden("sim2real_reward", CR)
     G = lambda name: rows(g[kind + "_" + name], n)  # noqa: E731
     episode_len = 4
     sim_steps = (np.arange(n) * 3) % 9
-    H = Buffers(n, G("position"), G("orientation"), G("vehicle_orientation"), G("body_linvel"), G("body_angvel"), crashes=G("crashes_in"),
+    H = Buffers(n, G("position"), G("orientation"), vehicle_orientation=G("vehicle_orientation"), body_linvel=G("body_linvel"),
+                body_angvel=G("body_angvel"), crashes=G("crashes_in"),
                 sim_steps=sim_steps)
     p = H._lib.dptr
     target, act, pact, pd = soa(G("target")), dev(G("actions")), dev(G("prev_actions")), dev(G("prev_dist"))
@@ -124,10 +52,11 @@ def test_reward_kernel_equals_the_reference_bit_for_bit(kind, k, n):
 
 
 def test_reward_kernel_without_reset_on_collision_and_on_the_other_parity():
-    g = load_golden("sim2real_reward", cr=True)
+    g = load_golden("sim2real_reward", CR)
     n, kind, k = 65, "velocity", R.VELOCITY
     G = lambda name: rows(g[kind + "_" + name], n)  # noqa: E731
-    H = Buffers(n, G("position"), G("orientation"), G("vehicle_orientation"), G("body_linvel"), G("body_angvel"), crashes=G("crashes_in"), parity=0)
+    H = Buffers(n, G("position"), G("orientation"), vehicle_orientation=G("vehicle_orientation"), body_linvel=G("body_linvel"),
+                body_angvel=G("body_angvel"), crashes=G("crashes_in"), parity=0)
     p = H._lib.dptr
     target, act, pact, pd = soa(G("target")), dev(G("actions")), dev(G("prev_actions")), dev(G("prev_dist"))
     rew = torch.zeros(n, device=DEV)
@@ -140,7 +69,7 @@ def test_reward_kernel_without_reset_on_collision_and_on_the_other_parity():
 
 @pytest.mark.parametrize("n", SIZES)
 def test_obs_kernel_equals_the_reference_bit_for_bit(n):
-    g = load_golden("sim2real_obs", cr=True)
+    g = load_golden("sim2real_obs", CR)
     G = lambda name: rows(g[name], n)  # noqa: E731
     s = G("state")
     H = Buffers(n, s[:, 0:3], s[:, 3:7], body_linvel=G("body_linvel"), body_angvel=G("body_angvel"), robot_actions=G("robot_actions"))
@@ -178,7 +107,7 @@ def pre_step_rows(g, kind, steps):
 def test_pre_step_kernel_equals_the_reference_bit_for_bit(kind, k, aliased, n):
     """aliased: the caller reuses ONE action buffer, so task.actions and the incoming tensor are the same memory (steps 1-6 of the
     golden); otherwise the previous call's tensor is another one (all steps)."""
-    g = load_golden("sim2real_glue", cr=True)
+    g = load_golden("sim2real_glue", CR)
     d = pre_step_rows(g, kind, range(1, 7) if aliased else range(1, 12))
     D = lambda name: rows(d[name], n)  # noqa: E731
     H = Buffers(n, D("pre_position"), D("pre_orientation"))
@@ -199,55 +128,6 @@ def test_pre_step_kernel_equals_the_reference_bit_for_bit(kind, k, aliased, n):
     assert same(host(H.state).T[:, 0:7], np.concatenate([D("pre_position"), D("pre_orientation")], axis=1))
 
 
-class RecordingSource:
-    """the env's random source, passing every call through to torch and keeping what the normal fills returned"""
-
-    def __init__(self, device):
-        from aerial_gym_simulator_amd.utils.random_source import TorchRandomSource
-
-        self.inner = TorchRandomSource(device)
-        self.normals, self.calls = [], []
-
-    def rand(self, *shape, tag=""):
-        self.calls.append(("rand", tuple(shape), tag))
-        return self.inner.rand(*shape, tag=tag)
-
-    def rand_into(self, out, tag=""):
-        self.calls.append(("rand", tuple(out.shape), tag))
-        return self.inner.rand_into(out, tag=tag)
-
-    def bernoulli(self, p, *shape, tag=""):
-        self.calls.append(("bernoulli", tuple(shape), tag))
-        return self.inner.bernoulli(p, *shape, tag=tag)
-
-    def normal_into(self, out, tag=""):
-        self.calls.append(("normal", tuple(out.shape), tag))
-        r = self.inner.normal_into(out, tag=tag)
-        self.normals.append(out.detach().clone())
-        return r
-
-    def gauss(self, mean, std):
-        return self.inner.gauss(mean, std)
-
-
-def offset_consumed_by(calls):
-    """how far the listed fills move the default generator's offset (on a saved and restored generator state)"""
-    gen = torch.cuda.default_generators[0]
-    state = gen.get_state()
-    try:
-        start = gen.get_offset()
-        for what, shape, _ in calls:
-            if what == "bernoulli":
-                torch.bernoulli(torch.full(shape, 0.5, device=DEV))
-            elif what == "normal":
-                torch.empty(shape, device=DEV).normal_()
-            else:
-                torch.empty(shape, device=DEV).uniform_()
-        return gen.get_offset() - start
-    finally:
-        gen.set_state(state)
-
-
 @pytest.mark.parametrize("strict", [False, True])
 @pytest.mark.parametrize("kind,k", KINDS)
 def test_task_trace_equals_the_restatement_on_the_dict_tensors(kind, k, strict):
@@ -259,7 +139,7 @@ def test_task_trace_equals_the_restatement_on_the_dict_tensors(kind, k, strict):
     n, steps, episode_len = 65, 60, 20
     cfg = task_registry.get_task_config(NAMES[kind])
     rs = RecordingSource(DEV)
-    with config_restored(cfg):
+    with config_restored(cfg, CONFIG_KEYS):
         cfg.args = {"ray_cast_sensors": "off", "random_source": rs, "strict_rng": strict}
         cfg.episode_len_steps = episode_len
         task = task_registry.make_task(NAMES[kind], seed=11, num_envs=n, headless=True)
@@ -354,7 +234,7 @@ def test_trainer_default_env_name_builds_and_steps_through_the_alias():
     from aerial_gym.config.task_config.position_setpoint_task_sim2real_config import task_config
     from aerial_gym.registry.task_registry import task_registry
 
-    with config_restored(task_config):
+    with config_restored(task_config, CONFIG_KEYS):
         task = task_registry.make_task("position_setpoint_task_sim2real", num_envs=128, headless=True)
         obs = task.reset()[0]
         for _ in range(3):
@@ -381,7 +261,7 @@ def test_reference_trained_lmf2_policies_fly_the_tasks_on_their_own_noisy_observ
     g = np.load(os.path.join(os.path.dirname(GOLDEN), LMF2[kind][0]))
     actor = Actor(g).to(DEV).eval()
     cfg = task_registry.get_task_config(NAMES[kind])
-    with config_restored(cfg):
+    with config_restored(cfg, CONFIG_KEYS):
         task = task_registry.make_task(NAMES[kind], seed=42, num_envs=n, headless=True)
         d = task.obs_dict
         obs = task.reset()[0]

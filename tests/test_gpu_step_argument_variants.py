@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from aerial_gym_simulator_amd import _lib
+from task_test_util import npy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -66,10 +67,6 @@ def _restore():
 
 
 _ROC_TOUCHED = []  # (env config class, its reset_on_collision before a test changed it)
-
-
-def npy(t):
-    return np.ascontiguousarray(t.detach().cpu().numpy())
 
 
 class _Task:

@@ -10,14 +10,11 @@ import numpy as np
 import pytest
 import radar_ref as R
 from conftest import GOLDEN, ROOT, rel_err
+from task_test_util import load_golden
 
 NAME = "radar_navigation_task"
+CR = "radar_cr"  # the fixtures made by the reference's code with correctly rounded elementary functions
 FIXTURES = ("radar_reward", "radar_image_obs", "radar_config")
-
-
-def load_golden(name, cr=False):
-    """cr=True: the fixture made by the reference's code with correctly rounded elementary functions (tests/golden/radar_cr/)"""
-    return np.load(os.path.join(GOLDEN, *(["radar_cr"] if cr else []), name + ".npz"))
 
 
 def reward_of(g, radar=True):
@@ -120,9 +117,9 @@ def test_make_task_builds_the_radar_recipe():
 
 
 def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit(orc):
-    g = load_golden("radar_reward", cr=True)
+    g = load_golden("radar_reward", CR)
     assert np.array_equal(reward_of(g), g["reward"]) and np.array_equal(reward_of(g, radar=False), g["reward_lidar_formula"])
-    g = load_golden("radar_image_obs", cr=True)
+    g = load_golden("radar_image_obs", CR)
     clean, noisy = images_of(orc, g)
     assert np.array_equal(clean[0], g["clean_ttc"]) and np.array_equal(clean[1], g["clean_ds"])
     assert np.array_equal(noisy[0], g["noisy_ttc"]) and np.array_equal(noisy[1], g["noisy_ds"])
@@ -143,14 +140,14 @@ def test_restatement_against_the_plain_torch_reference(orc):
 
 @pytest.mark.parametrize("cr", [False, True])
 def test_goldens_are_what_they_claim(cr):
-    g = load_golden("radar_reward", cr=cr)
+    g = load_golden("radar_reward", CR if cr else None)
     n = g["reward"].shape[0]
     dist = np.linalg.norm(g["pos_err"], axis=1)
     assert n == 768 and (g["vveh"][:, 0] > 0).sum() >= 200 and (g["vveh"][:, 0] < 0).sum() >= 200
     assert (dist < 1).sum() >= 50 and ((dist > 1) & (dist < 3)).sum() >= 50 and (dist > 3).sum() >= 50
     assert 30 <= g["crashes"].sum() <= 150 and (g["reward"][g["crashes"]] == g["rp"][21]).all()
     assert (g["reward"] != g["reward_lidar_formula"]).sum() >= 200
-    g = load_golden("radar_image_obs", cr=cr)
+    g = load_golden("radar_image_obs", CR if cr else None)
     assert g["pointcloud"].shape == (6, 1, 48, 120, 3) and g["noisy_ds"].shape == (6, 320)
     nm, im = g["noise_mask"].reshape(6, 320) == 1, g["invalid_mask"].reshape(6, 320) == 1
     assert (nm & ~im).sum() >= 5 and (nm & im).sum() >= 20 and abs(im.mean() - 0.8) <= 0.05
@@ -177,7 +174,7 @@ def test_generator_reproduces_the_committed_goldens(cr, tmp_path):
     subprocess.run(cmd, check=True, capture_output=True, timeout=600)
     assert sorted(os.listdir(tmp_path)) == sorted(n + ".npz" for n in FIXTURES)
     for name in FIXTURES:
-        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, cr=cr)
+        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, CR if cr else None)
         assert sorted(a.files) == sorted(b.files), name
         for key in b.files:
             assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (name, key)

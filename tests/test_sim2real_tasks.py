@@ -1,7 +1,6 @@
 """CPU: the two lmf2 sim2real set-point tasks -- registry, configs, the `aerial_gym` alias, the opt-in env argument, and the numpy
 restatement the GPU tests compare against (tests/sim2real_ref.py) pinned to the reference's own code through
 tests/golden/sim2real_*.npz, tests/golden/sim2real_cr/ (tests/golden_gen/gen_golden_sim2real.py)."""
-import contextlib
 import json
 import os
 import subprocess
@@ -11,36 +10,14 @@ import numpy as np
 import pytest
 import sim2real_ref as R
 import torch
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
+from task_test_util import config_restored, load_golden
+from task_test_util import same_bits as same
 
+CR = "sim2real_cr"  # the fixtures made by the reference's code with correctly rounded elementary functions
+CONFIG_KEYS = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps")
 KINDS = (("velocity", R.VELOCITY), ("acceleration", R.ACCELERATION))
 NAMES = {"velocity": "position_setpoint_task_sim2real", "acceleration": "position_setpoint_task_acceleration_sim2real"}
-
-
-def load_golden(name, cr=False):
-    """cr=True: the fixture made by the reference's code with correctly rounded elementary functions (tests/golden/sim2real_cr/)"""
-    return np.load(os.path.join(GOLDEN, *(["sim2real_cr"] if cr else []), name + ".npz"))
-
-
-@contextlib.contextmanager
-def config_restored(cfg):
-    """make_task writes its arguments into the (shared) config class: put everything back"""
-    keys = ("seed", "num_envs", "headless", "device", "use_warp", "args", "episode_len_steps")
-    old = {k: getattr(cfg, k) for k in keys}
-    try:
-        yield cfg
-    finally:
-        for k, v in old.items():
-            setattr(cfg, k, v)
-
-
-def bits(a):
-    a = np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32) if a.dtype.kind == "f" else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def test_registry_holds_both_tasks_and_configs_equal_the_reference():
@@ -91,7 +68,7 @@ def test_tasks_build_with_the_reference_attributes(kind, k):
     import aerial_gym_simulator_amd as ag
 
     cfg = ag.task_registry.get_task_config(NAMES[kind])
-    with config_restored(cfg):
+    with config_restored(cfg, CONFIG_KEYS):
         cfg.device = "cpu"
         t = ag.task_registry.make_task(NAMES[kind], num_envs=8, headless=True)
     for name in ("actions", "prev_actions", "actions_vehicle_frame", "prev_actions_vehicle_frame"):
@@ -151,7 +128,7 @@ def replay_glue(g, kind, k):
 def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit():
     """every env of every golden: reward, crashes, vehicle-frame actions; observation and quaternion write-back (w < 0, w = +-0,
     yaw next to +-pi among the rows); every array the reference's real step() produced on the scripted simulator"""
-    g = load_golden("sim2real_reward", cr=True)
+    g = load_golden("sim2real_reward", CR)
     for kind, k in KINDS:
         r = reward_outputs(g, kind, k)
         assert same(r["reward"], g[kind + "_reward"]), kind
@@ -160,13 +137,13 @@ def test_restatement_equals_the_correctly_rounded_reference_bit_for_bit():
             assert same(r["actions_vehicle_frame"], g[kind + "_actions_vehicle_frame"])
         dist = r["dist"]
         assert (dist < 0.2).sum() > 50 and (dist > 10).sum() > 10 and 100 < (dist < g[kind + "_prev_dist"]).sum() < 668
-    g = load_golden("sim2real_obs", cr=True)
+    g = load_golden("sim2real_obs", CR)
     obs, q = obs_outputs(g)
     assert same(obs, g["obs"]) and same(q, g["orientation_after"])
     w = g["state"][:, 6]
     assert (w < 0).sum() > 20 and w[0] == 0 and not np.signbit(w[0]) and w[1] == 0 and np.signbit(w[1])
     assert not g["orientation_after"][0:2].any()  # sign(+-0) = 0: the reference zeroes the quaternion there
-    g = load_golden("sim2real_glue", cr=True)
+    g = load_golden("sim2real_glue", CR)
     for kind, k in KINDS:
         out = replay_glue(g, kind, k)
         for name, v in out.items():
@@ -227,7 +204,7 @@ def test_generator_reproduces_the_committed_goldens(cr, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "tests", "golden_gen", "gen_golden_sim2real.py"), "--out", str(tmp_path)] + (["--cr"] if cr else [])
     subprocess.run(cmd, check=True, capture_output=True, timeout=600)
     for name in ("sim2real_reward", "sim2real_obs", "sim2real_glue", "sim2real_config"):
-        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, cr=cr)
+        a, b = np.load(tmp_path / (name + ".npz")), load_golden(name, CR if cr else None)
         assert sorted(a.files) == sorted(b.files), name
         for key in b.files:
             assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), (name, key)
