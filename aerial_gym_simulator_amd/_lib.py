@@ -135,6 +135,7 @@ class AgxImuArgs(C.Structure):
         ("world_frame", C.c_int32),
         ("enable_noise", C.c_int32),
         ("enable_bias", C.c_int32),
+        ("gravity", C.c_float * 3),
     ]
 
 
@@ -297,7 +298,7 @@ class AgxComOffset(C.Structure):
     _fields_ = [("c", C.c_float * 3), ("reserved", C.c_float)]
 
 
-ABI_VERSION = 19  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 20  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),

@@ -6,7 +6,8 @@
 
 namespace agx {
 
-// 6 normals of (env, step, sub-step, which): Philox blocks 3*slot .. 3*slot+2 -> 12 uniforms -> 6 normals
+// 6 normals of (env, step, slot): Philox blocks 3*slot .. 3*slot+2 of RNG_IMU are 12 uniforms, of which the first two of each
+// block make one Box-Muller pair (uniforms 0,1 -> z0,z1; 4,5 -> z2,z3; 8,9 -> z4,z5); the other six are not used (agx_rng.h)
 AGX_DEV void normals6(uint64_t seed, int env, int step, int slot, float z[6]) {
   float u[12];
 #pragma unroll
@@ -26,10 +27,11 @@ __global__ void __launch_bounds__(256) k_imu_update(AgxEnvBuffers B, int n, int 
   if (i >= n) return;
   const Q4 q = Q4{B.state[3 * n + i], B.state[4 * n + i], B.state[5 * n + i], B.state[6 * n + i]};
   const V3 wb = V3{B.derived[13 * n + i], B.derived[14 * n + i], B.derived[15 * n + i]};  // robot_body_angvel
-  const V3 g = V3{A.g_world[0], A.g_world[1], A.g_world[2]};
-  // force sensor on the base link: total force incl. gravity, body frame
+  const V3 g = V3{A.g_world[0], A.g_world[1], A.g_world[2]};  // what the sensor subtracts: 0 with gravity_compensation
+  // force sensor on the base link: total force incl. gravity, body frame -- the gravity the simulation runs under, with or
+  // without gravity_compensation (isaacgym_asset.py:41-42, imu_sensor.py:89)
   const V3 fb = V3{B.body_force[0 * n + i], B.body_force[1 * n + i], B.body_force[2 * n + i]};
-  const V3 gb = quat_rotate_inverse(q, g);
+  const V3 gb = quat_rotate_inverse(q, V3{A.gravity[0], A.gravity[1], A.gravity[2]});
   const V3 at = V3{(fb.x + A.mass * gb.x) / A.mass, (fb.y + A.mass * gb.y) / A.mass, (fb.z + A.mass * gb.z) / A.mass};
   const float *sq = sensor_quat + (size_t)i * 4;
   const Q4 qs = Q4{sq[0], sq[1], sq[2], sq[3]};
@@ -109,6 +111,9 @@ extern "C" int agx_imu_update(const AgxEnvBuffers *B, int n, int k, const AgxImu
   AGX_REQUIRE(sensor_quat && bias && imu_meas, "null buffer");
   AGX_REQUIRE((z_noise == nullptr) == (z_bias == nullptr) || k == 0, "z_noise and z_bias: both tensors or both NULL");
   AGX_REQUIRE(A->mass > 0.0f && A->sqrt_dt > 0.0f, "mass and sqrt_dt must be positive");
+  const bool compensated = A->g_world[0] == 0.0f && A->g_world[1] == 0.0f && A->g_world[2] == 0.0f;
+  AGX_REQUIRE(compensated || (A->g_world[0] == A->gravity[0] && A->g_world[1] == A->gravity[1] && A->g_world[2] == A->gravity[2]),
+              "AgxImuArgs: g_world is gravity * (1 - gravity_compensation), so zero or equal to `gravity` (a caller from before ABI 20 fills g_world only)");
   hipLaunchKernelGGL(k_imu_update, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *B, n, k, *A, sensor_quat, z_noise,
                      z_bias, bias, imu_meas);
   return check_launch("agx_imu_update");

@@ -29,7 +29,10 @@ enum {
   RNG_OBS_NOISE = 6,    // counter word 1 = env step; 6 draws                    (agx_obs_lidar_navigation)
   RNG_IMU_RESET = 7,    // counter word 1 = episode; 9 draws                     (agx_imu_reset)
   RNG_TARGET = 9,       // counter word 1 = episode; 4 draws (target ratio xyz, target yaw) (agx_nav_target_reset)
-  RNG_IMU = 8,          // counter word 1 = env step; block = 3 * sub-step + j   (agx_imu_update)
+  RNG_IMU = 8,          // counter word 1 = env step; block = 3 * slot + j, j = 0..2 (agx_imu_update).  Slot 2 s is the noise of
+                        // physics sub-step s (only that of the last one, 2 (k - 1), is drawn), slot 2 s + 1 its bias increment.
+                        // Channel pair (2 j, 2 j + 1) of a slot is the Box-Muller pair of uniforms 0 and 1 of block 3 * slot + j:
+                        // (u[0], u[1]), (u[4], u[5]), (u[8], u[9]) of the slot's twelve; uniforms 2 and 3 of a block are not used
   RNG_E2E_OBS_NOISE = 10,  // counter word 1 = env step; 12 draws -> 12 normals    (agx_end_to_end_obs, agx_post_step_end_to_end)
   RNG_RADAR_NOISE = 11,  // counter word 1 = env step; block = pooled cell       (agx_radar_image_obs)
   RNG_ASSETS = 16,      // + asset index (< 2^16 assets)

@@ -35,6 +35,7 @@ class IMUSensor:
         grav = g["sim_config"].sim.gravity
         for i in range(3):
             A.min_rot[i], A.max_rot[i] = math.radians(cfg.min_euler_rotation_deg[i]), math.radians(cfg.max_euler_rotation_deg[i])
+            A.gravity[i] = grav[i]  # the force sensor reads the total force under the simulation's gravity, compensated or not
             A.g_world[i] = grav[i] * (1 - int(self.gravity_compensation))
         A.sqrt_dt = self.sqrt_dt
         A.mass = float(g["robot_mass"][0])

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 19
+#define AGX_ABI_VERSION 20
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -582,7 +582,9 @@ int agx_sensor_mount_reset(const AgxEnvBuffers *buf, int num_envs, int num_senso
 
 /* ---- IMU (aerial_gym/sensors/imu_sensor.py:74-153) ------------------------------------------
  * The reference reads Isaac Gym's force sensor on the base link (total force incl. gravity, body
- * frame) every physics sub-step; here the same quantity is m * (body_force / m + R^T g).
+ * frame) every physics sub-step; here the same quantity is m * (body_force / m + R^T gravity),
+ * with the gravity the simulation runs under whatever gravity_compensation says: the flag only
+ * decides what the sensor subtracts again (g_world).
  * agx_imu_update is called once per env step after agx_env_step with the same k: the bias random
  * walk takes k steps (z_bias [k][N][6] normal draws), noise (z_noise [N][6]) and the measurement are
  * those of the last sub-step.  z_noise == z_bias == NULL: device generator (Box-Muller on the
@@ -591,9 +593,11 @@ int agx_sensor_mount_reset(const AgxEnvBuffers *buf, int num_envs, int num_senso
 typedef struct AgxImuArgs {
   float bias_std[6], noise_std[6], max_value[6], max_bias_init[6];
   float min_rot[3], max_rot[3]; /* sensor mount perturbation, radians                              */
-  float g_world[3];             /* gravity * (1 - gravity_compensation)                            */
+  float g_world[3];             /* gravity * (1 - gravity_compensation): what the sensor subtracts */
   float sqrt_dt, mass;
   int32_t world_frame, enable_noise, enable_bias;
+  float gravity[3];             /* the simulation's gravity: what the force sensor's reading holds
+                                   (g_world must be zero or equal to it: anything else is refused)  */
 } AgxImuArgs;
 int agx_imu_update(const AgxEnvBuffers *buf, int num_envs, int k_substeps, const AgxImuArgs *args,
                    const float *sensor_quat, const float *z_noise, const float *z_bias, float *bias,

@@ -53,6 +53,22 @@ def test_struct_layouts_match_header(tmp_path):
                      ctypes.sizeof(_lib.AgxLinkFrames), ctypes.sizeof(_lib.AgxStrictStepPlan)]
 
 
+def test_imu_args_fields_match_header(tmp_path):
+    """AgxImuArgs field by field: the offset of every member in C == the ctypes mirror's (the sensor's two gravity vectors are three
+    floats each and sizeof alone would not notice them swapped); `gravity` was appended, the older members keep their offsets."""
+    from aerial_gym_simulator_amd import _lib
+
+    names = [name for name, _ in _lib.AgxImuArgs._fields_]
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "aerial_gym_hip.h"\nint main(){'
+           + "".join('printf("%%zu\\n", offsetof(AgxImuArgs, %s));' % name for name in names) + "return 0;}")
+    exe = str(tmp_path / "agx_imu_offsets")
+    subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src, text=True, check=True)
+    offsets = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
+    assert offsets == [getattr(_lib.AgxImuArgs, name).offset for name in names]
+    assert names[-1] == "gravity" and names.index("g_world") == 6 and _lib.AgxImuArgs.g_world.offset == 120
+    assert _lib.AgxImuArgs.gravity.offset == 152 and ctypes.sizeof(_lib.AgxImuArgs) == 164
+
+
 def test_product_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "aerial_gym_simulator_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -21,6 +21,7 @@ def _args(g, world_frame, gravity=(0.0, 0.0, -9.81)):
         A.bias_std[i], A.noise_std[i], A.max_value[i], A.max_bias_init[i] = g["bias_std"][i], g["noise_std"][i], g["max_value"][i], g["max_bias_init"][i]
     for i in range(3):
         A.min_rot[i], A.max_rot[i], A.g_world[i] = np.deg2rad(g["min_rot_deg"][i]), np.deg2rad(g["max_rot_deg"][i]), gravity[i]
+        A.gravity[i] = gravity[i]
     A.sqrt_dt, A.mass = float(np.sqrt(0.01)), float(g["mass"])
     A.world_frame, A.enable_noise, A.enable_bias = int(world_frame), 1, 1
     return A

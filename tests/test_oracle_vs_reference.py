@@ -340,6 +340,27 @@ def test_imu_matches_reference(orc, frame):
     assert np.abs(g[frame + "_meas"][-1][:8, 0:3]).max() == 100.0  # the clamp was exercised
 
 
+@pytest.mark.parametrize("frame", ["body", "world"])
+def test_imu_gravity_compensation_matches_reference(orc, frame):
+    """gravity_compensation = True under a tilted gravity: g_world = 0, so the reference returns the force sensor's reading over the
+    mass, rotated into the sensor frame, with nothing subtracted (imu_sensor.py:61-63, 89-106).  Handing the oracle the fixture's
+    gravity instead of zero is off by |gravity| = 9.3 m/s^2."""
+    g = load_golden("imu_sensor_gravity_compensation")
+    bias = g[frame + "_bias0"].copy()
+    sqrt_dt = np.float32(np.sqrt(0.01))
+    args = (g["bias_std"], g["noise_std"], g["max_value"])
+    for k in range(g[frame + "_force"].shape[0]):
+        rest = (g[frame + "_force"][k], g[frame + "_quat"][k], g[frame + "_wbody"][k], g[frame + "_sensor_quat"], g[frame + "_z_noise"][k],
+                g[frame + "_z_bias"][k])
+        wrong = orc.imu_update(float(g["mass"]), g["gravity"], sqrt_dt, frame == "world", 1, 1, *args, *rest, bias.copy())
+        meas = orc.imu_update(float(g["mass"]), [0.0, 0.0, 0.0], sqrt_dt, frame == "world", 1, 1, *args, *rest, bias)
+        assert rel_err(meas, g[frame + "_meas"][k]) < 2e-6, k
+        d = np.linalg.norm((wrong - g[frame + "_meas"][k])[:, :3].astype(np.float64), axis=1)
+        assert np.abs(d - np.linalg.norm(g["gravity"].astype(np.float64))).max() < 1e-4, k  # (no entry of this chain reaches a clamp)
+    assert rel_err(bias, g[frame + "_bias_end"]) < 1e-6
+    assert np.abs(g[frame + "_meas"][:, :, :3]).max() < 100.0
+
+
 def _compare_fixture_dirs(made_dir, committed_dir, names=None):
     import os
 
