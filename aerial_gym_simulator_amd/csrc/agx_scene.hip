@@ -38,9 +38,10 @@ __global__ void __launch_bounds__(256) k_scene_transform(int n, int nt, int na, 
                                                           const int32_t *__restrict__ tri_asset,
                                                           const float *__restrict__ asset_state,
                                                           const uint8_t *__restrict__ mask, float *__restrict__ tri_world) {
-  const int env = blockIdx.y;
+  // env on grid.x (2^31 blocks), triangle chunk on grid.y: HIP caps grid.y at 65535, the env count has no such bound
+  const int env = blockIdx.x;
   if (mask && !mask[env]) return;
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y * blockDim.x + threadIdx.x;
   if (f >= nt) return;
   transform_triangle(env, f, nt, na, tri_local, tri_asset, asset_state, tri_world);
 }
@@ -930,11 +931,15 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
 // with 2 % dirty envs).  Instead: one small workgroup compacts the dirty env ids into a work list and a
 // CU-sized persistent grid pulls envs from it through an atomic cursor (perfect balance, no idle slots).
 //   work[0] = number of dirty envs, work[1] = cursor, work[2 ...] = env ids
-__global__ void __launch_bounds__(1024) k_compact_mask(int n, const uint8_t *__restrict__ mask, int32_t *__restrict__ work) {
+// flag != nullptr: the step's reset flag word -- 0 means no env resets whatever the mask holds (what k_reset_assets and the
+// one-launch refresh read), and the list stays empty
+__global__ void __launch_bounds__(1024) k_compact_mask(int n, const uint8_t *__restrict__ mask, int32_t *__restrict__ work,
+                                                        const int32_t *__restrict__ flag) {
   __shared__ int count;
   if (threadIdx.x == 0) count = 0;
   __syncthreads();
-  for (int env = threadIdx.x; env < n; env += blockDim.x)
+  const bool any = !flag || *flag != 0;
+  for (int env = threadIdx.x; any && env < n; env += blockDim.x)
     if (mask[env]) work[2 + atomicAdd(&count, 1)] = env;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1051,7 +1056,8 @@ extern "C" int agx_scene_transform(int n, int nt, int na, const float *tri_local
                                    const float *asset_state, const uint8_t *mask, float *tri_world, void *stream) {
   AGX_REQUIRE(n > 0 && nt > 0 && na > 0, "bad sizes n=%d nt=%d na=%d", n, nt, na);
   AGX_REQUIRE(tri_local && tri_asset && asset_state && tri_world, "null buffer");
-  dim3 grid(blocks_for(nt, 256), n);
+  AGX_REQUIRE(blocks_for(nt, 256) <= 65535, "num_tris %d: more than 65535 chunks of 256 triangles per env (grid.y)", nt);
+  dim3 grid(n, blocks_for(nt, 256));
   hipLaunchKernelGGL(k_scene_transform, grid, dim3(256), 0, (hipStream_t)stream, n, nt, na, tri_local, tri_asset, asset_state,
                      mask, tri_world);
   return check_launch("agx_scene_transform");
@@ -1061,6 +1067,7 @@ extern "C" int agx_boxes_from_assets(int n, int na, const float *asset_state, co
                                      float *boxes, void *stream) {
   AGX_REQUIRE(n > 0 && na > 0, "bad sizes");
   AGX_REQUIRE(asset_state && half_extents && boxes, "null buffer");
+  AGX_REQUIRE(na <= 65535, "num_assets %d: more than 65535 boxes per env (grid.y is the box index)", na);
   dim3 grid(blocks_for(n, 256), na);
   hipLaunchKernelGGL(k_boxes_from_assets, grid, dim3(256), 0, (hipStream_t)stream, n, na, asset_state, half_extents, mask, boxes);
   return check_launch("agx_boxes_from_assets");
@@ -1133,7 +1140,7 @@ constexpr int kDirectRefreshEnvs = 2048;  // up to here a workgroup per env (cle
 // the masked refresh: direct (one workgroup per env, optionally with the asset reset in it) or compaction + persistent grid
 static int scene_refresh_launch(int n, int nt, int na, const float *tri_local, const int32_t *tri_asset, float *asset_state,
                                 const float *half_extents, int prims_per_object, const uint8_t *mask, float *tri_world, float *boxes,
-                                float *nodes, int32_t *work, const SceneResetArgs *reset, void *stream) {
+                                float *nodes, int32_t *work, const SceneResetArgs *reset, const int32_t *flag, void *stream) {
   static bool attr_set[2] = {false, false};
   const bool obj = object_level_build(nt, prims_per_object);
   auto kernel = obj ? k_scene_refresh<true> : k_scene_refresh<false>;
@@ -1147,7 +1154,7 @@ static int scene_refresh_launch(int n, int nt, int na, const float *tri_local, c
                        tri_asset, asset_state, half_extents, tri_world, boxes, work, nodes, mask, S);
     return check_launch("agx_scene_refresh");
   }
-  hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work);
+  hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, flag);
   const int grid = n < 512 ? n : 512;  // two resident workgroups per CU (LDS bound: 72 KB each for T = 1272 triangle-level, 41 KB object-level)
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad, prims_per_object, na, tri_local,
                      tri_asset, asset_state, half_extents, tri_world, boxes, work, nodes, (const uint8_t *)nullptr, S);
@@ -1167,7 +1174,7 @@ extern "C" int agx_scene_refresh(int n, int nt, int na, const float *tri_local, 
   }
   AGX_REQUIRE(work, "a masked refresh needs the work buffer (int32[num_envs + 2])");
   return scene_refresh_launch(n, nt, na, tri_local, tri_asset, const_cast<float *>(asset_state), half_extents, prims_per_object, mask, tri_world, boxes,
-                              nodes, work, nullptr, stream);
+                              nodes, work, nullptr, nullptr, stream);
 }
 
 // AssetManager.reset_idx + the geometry refresh behind it (agx_reset_assets + agx_scene_refresh) for the envs of buf->reset_mask, device
@@ -1186,10 +1193,10 @@ extern "C" int agx_scene_reset_refresh(const AgxEnvBuffers *B, int n, int nt, in
   if (n > kDirectRefreshEnvs) {
     if (int e = agx_reset_assets(B, n, na, R, nullptr, nullptr, nullptr, min_ratio, max_ratio, num_obstacles, num_keep, asset_state, stream)) return e;
     return scene_refresh_launch(n, nt, na, tri_local, tri_asset, asset_state, half_extents, prims_per_object, B->reset_mask, tri_world, boxes, nodes,
-                                work, nullptr, stream);
+                                work, nullptr, B->reset_flag + B->flag_parity, stream);
   }
   return scene_refresh_launch(n, nt, na, tri_local, tri_asset, asset_state, half_extents, prims_per_object, B->reset_mask, tri_world, boxes, nodes, work,
-                              &S, stream);
+                              &S, nullptr, stream);
 }
 
 extern "C" int agx_bvh_build(int n, int nt, int prims_per_object, const float *tri_world, const uint8_t *mask, float *nodes,
@@ -1203,7 +1210,7 @@ extern "C" int agx_bvh_build(int n, int nt, int prims_per_object, const float *t
   int npad = 0;
   size_t lds = 0;
   if (int e = bvh_launch_shape(nt, prims_per_object, &npad, &lds, reinterpret_cast<const void *>(kernel), &attr_set[obj])) return e;
-  if (mask) hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work);
+  if (mask) hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, (const int32_t *)nullptr);
   const int grid = n < 512 ? n : 512;  // two resident workgroups per CU (LDS bound: 72 KB each for T = 1272)
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad,
                      prims_per_object, tri_world, mask ? work : nullptr, nodes);  // (with the AGX_BVH_FULL_SORT bit, if set)

@@ -815,7 +815,8 @@ int agx_reset_assets(const AgxEnvBuffers *buf, int num_envs, int num_assets,
 
 /* WarpEnv.reset_idx (warp_env_manager.py:40-54): v_world = tf_apply(q_asset, p_asset, v).
  * tri_local/tri_world: [N][T][9] (a,b,c xyz); tri_asset: [T]; asset_state: [N][K][13].
- * Only envs with mask[env] != 0 are transformed (mask NULL = all).                    */
+ * Only envs with mask[env] != 0 are transformed (mask NULL = all).  The env is the launch's
+ * grid.x: no cap on num_envs from the grid; num_tris <= 65535 * 256 (chunks on grid.y).  */
 int agx_scene_transform(int num_envs, int num_tris, int num_assets, const float *tri_local,
                         const int32_t *tri_asset, const float *asset_state, const uint8_t *mask,
                         float *tri_world, void *stream);
@@ -875,7 +876,8 @@ int agx_bvh_build(int num_envs, int num_tris, int prims_per_object, const float 
                   const uint8_t *mask, float *nodes, int32_t *work, void *stream);
 
 /* Obstacle OBBs for the collision test, from the same asset poses:
- * boxes [K][11][N] <- asset_state [N][K][13], half_extents [N][K][3].                  */
+ * boxes [K][11][N] <- asset_state [N][K][13], half_extents [N][K][3]; row 10 of a box is
+ * its bounding radius |half_extents| * 1.000001.  num_assets <= 65535 (grid.y).         */
 int agx_boxes_from_assets(int num_envs, int num_assets, const float *asset_state,
                           const float *half_extents, const uint8_t *mask, float *boxes,
                           void *stream);
@@ -896,7 +898,8 @@ int agx_scene_refresh(int num_envs, int num_tris, int num_assets, const float *t
  * ONE launch -- a workgroup per env that resets the env's obstacle poses, moves its triangles and collision boxes and rebuilds its
  * tree; a clean env's workgroup leaves at once, a step without a reset costs one dispatch -- above, the three launches it replaces
  * at small batches (asset reset, mask compaction, persistent refresh).  num_assets = obstacles per env (one rigid piece each:
- * multi-primitive scenes keep agx_reset_assets + agx_prims_from_assets + agx_scene_refresh).  Same device functions either way. */
+ * multi-primitive scenes keep agx_reset_assets + agx_prims_from_assets + agx_scene_refresh).  Same device functions either way,
+ * and either way a step whose flag word buf->reset_flag[buf->flag_parity] is 0 changes nothing, whatever reset_mask holds.     */
 int agx_scene_reset_refresh(const AgxEnvBuffers *buf, int num_envs, int num_tris, int num_assets, const AgxResetArgs *args,
                             const float *min_ratio, const float *max_ratio, int num_obstacles, int num_keep, float *asset_state,
                             const float *tri_local, const int32_t *tri_asset, const float *half_extents, int prims_per_object,

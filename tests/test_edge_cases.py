@@ -35,6 +35,11 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert lib.agx_bvh_build(4, 24, 0, C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), None, None) == -1  # masked rebuild needs the work list
     assert lib.agx_raycast_camera(1, 1, 8, 8, (C.c_float * 4)(), 10.0, 4, 4, 9, None, None, None, None, None, 12, None, None, None, None) == -1
     assert lib.agx_bvh_nodes_bytes(3, 1272) == 3 * 1271 * 64
+    # grid.y carries the triangle chunk (scene transform) and the box index (collision boxes): 65535 of them at the most
+    assert lib.agx_scene_transform(4, 65535 * 256 + 1, 1, C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), None) == -1
+    assert b"num_tris 16776961" in lib.agx_last_error()
+    assert lib.agx_boxes_from_assets(4, 65536, C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), None) == -1
+    assert b"num_assets 65536" in lib.agx_last_error()
 
 
 @pytest.mark.gpu
@@ -193,3 +198,25 @@ def test_reset_assets_launches_beyond_65535_envs():
     assert float(p[placed].min()) >= -3.0 - 1e-5 and float(p[placed].max()) <= 3.0 + 1e-5
     assert float(p[-1].abs().sum()) > 0 and float(p[0].abs().sum()) > 0  # the last env was reached
     assert len(torch.unique(p[:, 0, 0])) > n // 2  # per-env draws
+
+
+@pytest.mark.gpu
+def test_scene_transform_launches_beyond_65535_envs(orc):
+    """agx_scene_transform puts the env on grid.x like agx_reset_assets: no 65535 cap on the env count (every unmasked
+    agx_scene_refresh comes through here).  Bit-equal to the oracle with and without a mask; the last env is reached."""
+    from obstacle_ref import bits_equal, random_asset_state, run_scene_transform, sentinel
+
+    n, nt, na = 70000, 2, 1
+    rng = np.random.default_rng(70000)
+    tri_local = rng.uniform(-2.0, 2.0, (n, nt, 9)).astype(np.float32)
+    tri_asset = np.zeros(nt, np.int32)
+    st = random_asset_state(rng, n, na)
+    ref = orc.scene_transform(tri_local, tri_asset, st)
+    init = sentinel((n, nt, 9))
+    mask = (rng.random(n) < 0.5).astype(np.uint8)
+    mask[-1], mask[-2], mask[65535], mask[65536] = 1, 0, 0, 1
+    for mk in (mask, None):
+        got = run_scene_transform(tri_local, tri_asset, st, mk, init)
+        want = ref if mk is None else np.where(mk.astype(bool)[:, None, None], ref, init)
+        assert bits_equal(got, want)
+        assert bits_equal(got[-1], ref[-1]) and not bits_equal(got[-1], init[-1])  # the last env was reached
