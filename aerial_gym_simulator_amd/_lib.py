@@ -298,7 +298,7 @@ class AgxComOffset(C.Structure):
     _fields_ = [("c", C.c_float * 3), ("reserved", C.c_float)]
 
 
-ABI_VERSION = 20  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 21  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -373,6 +373,9 @@ _SIGNATURES = {
     "agx_scene_refresh": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "agx_scene_reset_refresh": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, C.c_int, C.POINTER(AgxResetArgs), _P, _P, C.c_int, C.c_int, _P,
                                           _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "agx_bvh_large_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "agx_bvh_build_large": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "agx_scene_refresh_large": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "agx_sensor_pose": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "agx_raycast_camera": (
         C.c_int,

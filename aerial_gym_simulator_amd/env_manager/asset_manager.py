@@ -81,7 +81,7 @@ class AssetManager:
         N, K = sc.num_envs, sc.num_assets
         lib, stream, p = env._lib, env._stream(), _lib.dptr
         st = self.env_asset_state_tensor
-        if not env.strict_rng and not sc.has_prims and env.env_args.get("fused_asset_reset", True):
+        if not env.strict_rng and not sc.has_prims and not sc.large_build and env.env_args.get("fused_asset_reset", True):
             # obstacle poses, world-frame triangles, collision boxes and tree of the envs that reset: one call -- up to 2048 envs ONE
             # launch (the asset reset and the mask compaction are gone from the step), above, the three launches below
             _lib.check(
@@ -114,7 +114,13 @@ class AssetManager:
             _lib.check(lib.agx_prims_from_assets(N, KP, K, p(sc.prim_asset), p(st), p(sc.prim_local_pos), p(sc.prim_local_quat), mk,
                                                  p(sc.prim_state), stream), "agx_prims_from_assets")
             st = sc.prim_state
+        ppo = int(getattr(env, 'bvh_prims_per_object', None) or sc.bvh_prims_per_object)
+        if sc.large_build:  # above the LDS builders' cap (or forced): the build whose working arrays live in sc.bvh_scratch
+            _lib.check(lib.agx_scene_refresh_large(N, sc.num_tris, KP, p(sc.tri_local), p(sc.tri_asset), p(st), p(sc.half_extents), ppo, mk,
+                                                   p(sc.tri_world), p(sc.boxes_soa), p(sc.bvh_nodes), p(sc.bvh_work), p(sc.bvh_scratch),
+                                                   sc.bvh_scratch.numel(), stream), "agx_scene_refresh_large")
+            return
         # triangles -> world frame, collision boxes, LBVH: one call (masked: one persistent launch over the dirty envs)
         _lib.check(lib.agx_scene_refresh(N, sc.num_tris, KP, p(sc.tri_local), p(sc.tri_asset), p(st), p(sc.half_extents),
-                                         int(getattr(env, 'bvh_prims_per_object', None) or sc.bvh_prims_per_object), mk, p(sc.tri_world), p(sc.boxes_soa),
+                                         ppo, mk, p(sc.tri_world), p(sc.boxes_soa),
                                          p(sc.bvh_nodes), p(sc.bvh_work), stream), "agx_scene_refresh")

@@ -141,7 +141,8 @@ class EnvManager(BaseManager):
         rank = int(self.env_args.get("shard_rank", 0))
         self.env_offset = int(self.env_args.get("env_offset", rank * N))
         self.scene = SceneManager(env_cfg, N, dev, self.random_source, shard_rank=rank, env_offset=self.env_offset,
-                                  box_objects=bool(self.env_args.get("bvh_box_objects", True)))
+                                  box_objects=bool(self.env_args.get("bvh_box_objects", True)),
+                                  force_large_build=bool(self.env_args.get("bvh_large_build", False)))
         self.keep_in_env = self.scene.keep_in_env_num
         g["num_obstacles_in_env"] = self.scene.num_assets
         self.robot_manager = RobotManagerHIP(self.global_tensor_dict, self.cfg, self.robot_name, self.controller_name, dev,

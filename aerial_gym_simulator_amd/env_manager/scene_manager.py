@@ -8,7 +8,8 @@ Device data owned here
     tri_local     [N, T, 9]   box triangles in the asset frame (T = 12 K, trimesh box topology)
     tri_world     [N, T, 9]   after tf_apply(asset pose)   (rebuilt for reset envs)
     tri_seg       [N, T]      int32 segmentation id of the owning asset
-    bvh_nodes     [N, T-1, 16] LBVH built on device by agx_bvh_build
+    bvh_nodes     [N, T-1, 16] LBVH built on device by agx_bvh_build (agx_bvh_build_large above MAX_TRIS_PER_ENV triangles)
+    bvh_scratch   uint8        working memory of the large build (large_build scenes only)
     boxes_soa     [K*11, N]   OBBs (+ bounding radius) for the collision test
 """
 import os
@@ -28,7 +29,8 @@ _BOX_FACES = np.array(
 
 
 class SceneManager:
-    def __init__(self, env_cfg, num_envs, device, random_source, shard_rank=0, scene_seed_base=1000, env_offset=None, box_objects=True):
+    def __init__(self, env_cfg, num_envs, device, random_source, shard_rank=0, scene_seed_base=1000, env_offset=None, box_objects=True,
+                 force_large_build=False):
         self.cfg, self.num_envs, self.device = env_cfg, num_envs, device
         self.shard_rank = shard_rank
         # this process owns global envs [env_offset, env_offset + N)  (SURVEY 8e); equal shards: rank * N
@@ -54,10 +56,15 @@ class SceneManager:
         # cylinder / sphere / mesh keep their triangle subtrees.  box_objects=False (EnvManager args={"bvh_box_objects": False}):
         # triangle subtrees everywhere (A/B runs).
         self._box_objects = bool(box_objects)
+        self._force_large_build = bool(force_large_build)  # EnvManager args={"bvh_large_build": True}: A/B runs on a small scene
+        self.bvh_scratch = None
         # sharding: start of this rank's slice of the global asset counter
         semantic_offset = self.semantic_offset = env_offset * K  # this shard's slice of the global id counter
         if K == 0:
             return
+        if self.num_tris > self.MAX_TRIS_PER_ENV_LARGE:
+            raise ValueError(f"scene of {K} boxes = {self.num_tris} triangles per env exceeds the {self.MAX_TRIS_PER_ENV_LARGE} the tree build takes "
+                             "(csrc/agx_scene_large.hip kBvhLargeMaxTris): use fewer obstacles")
         size = np.zeros((N, K, 3), np.float32)
         lo = np.zeros((N, K, 13), np.float32)
         hi = np.zeros((N, K, 13), np.float32)
@@ -132,7 +139,25 @@ class SceneManager:
             return 12
         return 12 | 0x20000000 | (0 if self.has_prims else 0x10000000)
 
-    MAX_TRIS_PER_ENV = 2944  # csrc/agx_scene.hip kBvhMaxTris (agx_bvh_build refuses more by message; this names the assets)
+    MAX_TRIS_PER_ENV = 2944  # csrc/agx_scene.hip kBvhMaxTris: the LDS-resident builders (agx_bvh_build, agx_scene_refresh) take no more
+    MAX_TRIS_PER_ENV_LARGE = 65536  # csrc/agx_scene_large.hip kBvhLargeMaxTris (agx_bvh_build_large refuses more by message; this names the assets)
+
+    @property
+    def large_build(self):
+        """the tree comes from agx_scene_refresh_large (working arrays in bvh_scratch, global memory): scenes above the LDS
+        builders' cap, or any scene when forced"""
+        return self.num_assets > 0 and (self.num_tris > self.MAX_TRIS_PER_ENV or self._force_large_build)
+
+    def _alloc_bvh_scratch(self):
+        """once, in prepare_for_simulation: no step allocates"""
+        if not self.large_build:
+            return
+        from .. import _lib
+
+        need = int(_lib.load().agx_bvh_large_scratch_bytes(self.num_envs, self.num_tris))
+        if need <= 0:
+            raise ValueError(f"agx_bvh_large_scratch_bytes({self.num_envs}, {self.num_tris}) = {need}: the large tree build refuses this scene")
+        self.bvh_scratch = torch.zeros(need, dtype=torch.uint8, device=self.device)
 
     def _init_general(self, slots, variants, nk, nf, N, scene_seed_base, env_offset):
         """Scenes with multi-primitive assets (several links, cylinders): every primitive is its own rigid piece
@@ -151,11 +176,11 @@ class SceneManager:
         tri_count = np.array([t for ts in tri_s for t in ts], int)
         tri_base = np.concatenate([[0], np.cumsum(tri_count)]).astype(int)
         T = self.num_tris = int(tri_base[-1])
-        if T > self.MAX_TRIS_PER_ENV:
+        if T > self.MAX_TRIS_PER_ENV_LARGE:
             per_slot = sorted(((sum(ts), getattr(slots[s], "__name__", type(slots[s]).__name__)) for s, ts in enumerate(tri_s)), reverse=True)[:5]
             raise ValueError(
-                f"scene of {T} triangles per env exceeds the {self.MAX_TRIS_PER_ENV} the LDS-resident tree build takes "
-                f"(csrc/agx_scene.hip kBvhMaxTris); largest assets (triangles, type): {per_slot}.  A URDF sphere is 1280 triangles "
+                f"scene of {T} triangles per env exceeds the {self.MAX_TRIS_PER_ENV_LARGE} the tree build takes "
+                f"(csrc/agx_scene_large.hip kBvhLargeMaxTris); largest assets (triangles, type): {per_slot}.  A URDF sphere is 1280 triangles "
                 "(trimesh icosphere, 3 subdivisions) and a cylinder 128 (32 sections): use fewer of them, or box primitives")
         ids_per_slot = np.array([max(len(v) for v in vs) if getattr(t, "per_link_semantic", False) and t.semantic_id < 0 else 1
                                  for t, vs in zip(slots, variants)])
@@ -244,6 +269,7 @@ class SceneManager:
         self.boxes_soa = torch.zeros(K * 11, N, device=dev)
         self.bvh_nodes = torch.zeros(N, max(12 * K - 1, 1), 16, device=dev)
         self.bvh_work = torch.zeros(N + 2, dtype=torch.int32, device=dev)  # dirty-env work list of agx_bvh_build
+        self._alloc_bvh_scratch()
         g["scene_tri_world"] = self.tri_world
         g["scene_tri_seg"] = self.tri_seg
         g["scene_bvh_nodes"] = self.bvh_nodes
@@ -271,4 +297,5 @@ class SceneManager:
         self.boxes_soa = torch.zeros(KP * 11, N, device=dev)
         self.bvh_nodes = torch.zeros(N, max(T - 1, 1), 16, device=dev)
         self.bvh_work = torch.zeros(N + 2, dtype=torch.int32, device=dev)
+        self._alloc_bvh_scratch()
         g["scene_tri_world"], g["scene_tri_seg"], g["scene_bvh_nodes"] = self.tri_world, self.tri_seg, self.bvh_nodes

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 20
+#define AGX_ABI_VERSION 21
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -892,6 +892,27 @@ int agx_scene_refresh(int num_envs, int num_tris, int num_assets, const float *t
                       const int32_t *tri_asset, const float *asset_state, const float *half_extents,
                       int prims_per_object, const uint8_t *mask, float *tri_world, float *boxes,
                       float *nodes, int32_t *work, void *stream);
+
+/* Scenes above the LDS-resident build's 2944 triangles per env (the reference hands Warp whatever mesh it is given: the Warp
+ * mesh build / refit behind asset_manager.py:51-71, warp_env_manager.py:40-54, 162-166): the same LBVH -- same keys, order, tree and
+ * records, all prims_per_object forms; AGX_BVH_OBJECT_TREE and AGX_BVH_FULL_SORT are accepted and change nothing -- built with its
+ * working arrays in `scratch`, a caller-provided buffer in GLOBAL memory, for 2 <= num_tris <= 65536.  One workgroup builds one
+ * env, a persistent grid of at most 256 workgroups owns one slab of the scratch each: agx_bvh_large_scratch_bytes(num_envs,
+ * num_tris) = slabs x bytes per slab (about 40 B per triangle at the most) stops growing with num_envs at 256 envs and stays below 1 GiB.
+ * It returns 0 for sizes the build refuses.  mask / work as for agx_bvh_build.  At the cap a radix tree over the unique keys
+ * (32 bits of code with the parked marker, 16 of index) is at most 48 levels deep, below the ray-cast's 64-entry stack.
+ * agx_scene_refresh_large: agx_scene_refresh's arguments plus the scratch -- transform, collision boxes and this build for the
+ * envs of `mask`, or for every env.  All refuse by message before anything is launched: num_tris outside [2, 65536], null buffers,
+ * a mask without `work`, a scratch buffer smaller than required.  agx_bvh_build, agx_scene_refresh and agx_scene_reset_refresh
+ * keep their 2944 limit.                                                                                                        */
+size_t agx_bvh_large_scratch_bytes(int num_envs, int num_tris);
+int agx_bvh_build_large(int num_envs, int num_tris, int prims_per_object, const float *tri_world,
+                        const uint8_t *mask, float *nodes, int32_t *work, void *scratch, size_t scratch_bytes,
+                        void *stream);
+int agx_scene_refresh_large(int num_envs, int num_tris, int num_assets, const float *tri_local,
+                            const int32_t *tri_asset, const float *asset_state, const float *half_extents,
+                            int prims_per_object, const uint8_t *mask, float *tri_world, float *boxes,
+                            float *nodes, int32_t *work, void *scratch, size_t scratch_bytes, void *stream);
 
 /* AssetManager.reset_idx AND the geometry refresh behind it for the envs of buf->reset_mask (agx_reset_assets + agx_scene_refresh,
  * asset_manager.py:51-71 -> warp_env_manager.py:40-54), draws from the device generator (args->u_* NULL).  Up to 2048 envs this is
