@@ -186,6 +186,54 @@ def test_env_count_above_the_32_bit_offset_range_is_refused_without_a_gpu():
     assert lib.agx_update_states(B, 0, None) != 0 and "num_envs must be > 0" in lib.agx_last_error().decode()
 
 
+def test_raycast_launch_policy_gives_the_documented_splits():
+    """ray_split_policy / ray_launch_shape (csrc/agx_raycast.hip) restated, and read back through the thread count in
+    agx_raycast_kernel's name (host code only): the production values INTEGRATION.md and the policy's comment state -- about 4 tiles
+    per wave for cameras, about 2 for LiDARs -- and the small-batch rule, clamped to the image's tiles."""
+    import ctypes as C
+
+    from aerial_gym_simulator_amd import _lib
+
+    lib = _lib.load()
+    waves = 4  # kRayThreads / 64
+
+    def policy_split(images, width, height, lidar):
+        tw, th = (16, 4) if lidar else (8, 8)
+        tiles = -(-width // tw) * -(-height // th)
+        fill = -(-16384 // (images * waves))          # small batches: ~2 x the 8192 resident waves in the grid
+        local = tiles // (waves * (2 if lidar else 4))  # locality: 4 tiles per wave (camera), 2 (LiDAR)
+        return min(max(fill, local, 1), -(-tiles // waves)), tiles
+
+    def launched_split(n, ns, width, height, lidar, variant=0):
+        buf = C.create_string_buffer(128)
+        _lib.check(lib.agx_raycast_kernel(n, ns, width, height, int(lidar), variant, buf, 128), "agx_raycast_kernel")
+        name = buf.value.decode()
+        assert name.startswith(f"k_raycast<{'true' if lidar else 'false'},{variant}>_"), name
+        threads, per_split = int(name.rsplit("_", 1)[1]), -(-n * ns // 8) * 8 * 256
+        assert threads % per_split == 0, name
+        return threads // per_split
+
+    assert _lib.get_option("ray_split") == 0
+    # (envs, sensors, width, height, LiDAR) -> workgroups per image, tiles per wave
+    for (n, ns, w, h, lidar), (split, tiles_per_wave) in {(8192, 1, 64, 48, False): (3, 4),      # the depth-camera task
+                                                          (4096, 1, 512, 32, True): (32, 2),     # the 32 x 512 LiDAR
+                                                          (8192, 1, 120, 48, True): (12, 2),     # the LiDAR task's 48 x 120 dome
+                                                          (256, 1, 64, 48, False): (12, 1)}.items():  # small batch: fill 16 -> max_split
+        want, tiles = policy_split(n * ns, w, h, lidar)
+        assert want == split and -(-tiles // (split * waves)) == tiles_per_wave
+        for variant in range(3 if not lidar else 2):
+            assert launched_split(n, ns, w, h, lidar, variant) == split
+    # the option overrides the policy and is clamped to [1, max_split]; 0 puts the policy back
+    try:
+        for forced, split in ((1, 1), (2, 2), (12, 12), (13, 12), (1 << 20, 12)):
+            _lib.set_option("ray_split", forced)
+            assert launched_split(8192, 1, 64, 48, False) == split
+        assert lib.agx_set_option(b"ray_split", (1 << 20) + 1) != 0 and lib.agx_set_option(b"ray_split", -1) != 0
+    finally:
+        _lib.set_option("ray_split", 0)
+    assert launched_split(8192, 1, 64, 48, False) == 3
+
+
 def test_scene_manager_semantics():
     from aerial_gym_simulator_amd.sim.sim_builder import SimBuilder
 
