@@ -1,5 +1,7 @@
 // Scene kernels for gfx950: vertex transform at reset, obstacle OBBs for the collision
-// test, and an LBVH built per env entirely in LDS (one workgroup per env).
+// test, and an LBVH built per env entirely in LDS (one workgroup per env): a triangle-level builder and an object-level one.
+// What they share with each other and with the global-memory builder (agx_scene_large.hip) -- keys, radix tree, box-object
+// marking, child references, node records, the work-list loop, the host's argument rules -- is agx_bvh_parts.h.
 //
 // These replace WarpEnv.reset_idx's tf_apply over all vertices + per-env wp.Mesh.refit()
 // (warp_env_manager.py:40-54) and the wp.Mesh BVH build (warp_env_manager.py:162-166).
@@ -82,9 +84,6 @@ __device__ unsigned long long g_phase_clock[16];
 #define AGX_PHASE(k) do { } while (0)
 #define AGX_PHASE_LAST(k) do { } while (0)
 #endif
-#ifdef AGX_BVH_EXPERIMENT  // profiles/bvh_sah_experiment.py: object sort codes supplied by the host
-__device__ const uint32_t *g_obj_codes = nullptr;
-#endif
 
 // Multi-primitive assets (URDFs with several links: the reference's `trees`): every primitive is its own rigid
 // piece whose pose follows the asset's,  prim = asset (x) local.  prim_state [N][P][13] then plays the role of
@@ -154,13 +153,7 @@ AGX_DEV constexpr int bvh_box_floats_c(int nt, int threads) { return (nt - 1) * 
 // box of tree node c: internal nodes from LDS, leaves (c >= n_int) from their triangle, grown by kBoxEps
 AGX_DEV void node_box(const float *box, const unsigned long long *keys, const float *__restrict__ tris, int n_int, int c, float (&o)[6]) {
   if (c >= n_int) {
-    const int f = (int)(uint32_t)(keys[c - n_int] & 0xFFFFFFFFull);
-    const float *t = tris + (size_t)f * 9;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      o[k] = fminf(fminf(t[k], t[3 + k]), t[6 + k]) - kBoxEps;
-      o[3 + k] = fmaxf(fmaxf(t[k], t[3 + k]), t[6 + k]) + kBoxEps;
-    }
+    leaf_box(tris, key_index(keys[c - n_int]), o);
   } else {
 #pragma unroll
     for (int k = 0; k < 6; ++k) o[k] = box[(size_t)c * 6 + k];
@@ -214,20 +207,10 @@ AGX_DEV void bitonic_sort_lds(unsigned long long *keys, int m, int tid) {
 constexpr int kObjMax = 256;
 __host__ __device__ constexpr int obj_lds_bytes_c(int nt) { return kObjMax * (8 + 8 + 24 + 24 + 8 + 8 + 4 + 8 + 4 + 1 + 6) + (nt / 2) * 24 + 64; }
 
-AGX_DEV void obj_store_node(float *__restrict__ o, const float (&a)[6], const float (&b)[6], int rl, int rr, int sl, int sr) {
-  o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = __int_as_float(rl);
-  o[4] = a[3]; o[5] = a[4]; o[6] = a[5]; o[7] = __int_as_float(rr);
-  o[8] = b[0]; o[9] = b[1]; o[10] = b[2]; o[11] = __int_as_float(sl);
-  o[12] = b[3]; o[13] = b[4]; o[14] = b[5]; o[15] = __int_as_float(sr);
-}
 AGX_DEV void box_union(const float (&a)[6], const float (&b)[6], float (&o)[6]) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) { o[c] = fminf(a[c], b[c]); o[3 + c] = fmaxf(a[3 + c], b[3 + c]); }
 }
-
-// the six faces of trimesh's box by triangle pair: -x (0, 2)  +x (10, 11)  -y (1, 5)  +y (7, 9)  -z (3, 8)  +z (4, 6)
-AGX_DEV constexpr int pair_a(int fc) { return (int)((0x4371A0u >> (4 * fc)) & 15u); }  // nibble fc of 0x4371A0 / 0x6895B2 (the ray-cast kernel's face table)
-AGX_DEV constexpr int pair_b(int fc) { return (int)((0x6895B2u >> (4 * fc)) & 15u); }
 
 AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tri_world, float *__restrict__ nodes) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -250,15 +233,18 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
   // ---- phase 1: a thread per (object, face): the two triangles trimesh.creation.box puts on that face
   for (int t = tid; t < 6 * K; t += kBvhThreads) {
     const int obj = t / 6, fc = t - obj * 6;
-    const int qa = (int)((0x4371A0u >> (4 * fc)) & 15u), qb = (int)((0x6895B2u >> (4 * fc)) & 15u);  // kPairA / kPairB as nibbles
+    const int qa = pair_a(fc), qb = pair_b(fc);
     const float *to = tris + (size_t)obj * 12 * 9;
     float a[9], b[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) { a[k] = to[9 * qa + k]; b[k] = to[9 * qb + k]; }
+    float la[3], ha[3], lb[3], hb[3];
+    tri_bounds(a, la, ha);
+    tri_bounds(b, lb, hb);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      pb[6 * t + c] = fminf(fminf(fminf(a[c], a[3 + c]), a[6 + c]), fminf(fminf(b[c], b[3 + c]), b[6 + c]));
-      pb[6 * t + 3 + c] = fmaxf(fmaxf(fmaxf(a[c], a[3 + c]), a[6 + c]), fmaxf(fmaxf(b[c], b[3 + c]), b[6 + c]));
+      pb[6 * t + c] = fminf(la[c], lb[c]);
+      pb[6 * t + 3 + c] = fmaxf(ha[c], hb[c]);
     }
     bool ok = !tri_parked(to);
     if (ok) {
@@ -295,13 +281,13 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
           p0[c] = pb[6 * (6 * o + 2 * j) + c] - kBoxEps; p0[3 + c] = pb[6 * (6 * o + 2 * j) + 3 + c] + kBoxEps;
           p1[c] = pb[6 * (6 * o + 2 * j + 1) + c] - kBoxEps; p1[3 + c] = pb[6 * (6 * o + 2 * j + 1) + 3 + c] + kBoxEps;
         }
-        obj_store_node(rec + 16 * j, p0, p1, ~(g0 + pair_a(2 * j)), ~(g0 + pair_a(2 * j + 1)), g0 + pair_b(2 * j), g0 + pair_b(2 * j + 1));
+        store_node(rec + 16 * j, p0, p1, ~(g0 + pair_a(2 * j)), ~(g0 + pair_a(2 * j + 1)), g0 + pair_b(2 * j), g0 + pair_b(2 * j + 1));
         box_union(p0, p1, un[j]);
       }
-      obj_store_node(rec + 48, un[0], un[1], base + 0, base + 1, -1, -1);
+      store_node(rec + 48, un[0], un[1], base + 0, base + 1, -1, -1);
       float d[6];
       box_union(un[0], un[1], d);
-      obj_store_node(rec + 64, d, un[2], base + 3, base + 2, -1, -1);
+      store_node(rec + 64, d, un[2], base + 3, base + 2, -1, -1);
     }
     AGX_PHASE_LAST(8);
   }
@@ -310,7 +296,7 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
   // workgroup takes part in the five barriers between its steps.
   const int o = tid;
   const bool has_obj = tid < K;
-  float cen[3] = {0.0f, 0.0f, 0.0f}, big = -1.0f;
+  float oc[4] = {0.0f, 0.0f, 0.0f, -1.0f};  // the object's sort-centre record (object_sort_centre), in registers
   {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (has_obj) {
@@ -326,27 +312,18 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
         }
       }
       objok[o] = ok ? 1 : 0;
-      const bool parked = (fok[6 * o] & 2) != 0;
-      float bg = 0.0f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         oaabb[6 * o + c] = alo[c] - kBoxEps;      // (grown once, here: every box above is a union of these)
         oaabb[6 * o + 3 + c] = ahi[c] + kBoxEps;
-        cen[c] = 0.5f * (alo[c] + ahi[c]);
-        bg = fmaxf(bg, ahi[c] - alo[c]);
-        if (!parked) { lo[c] = fminf(lo[c], cen[c]); hi[c] = fmaxf(hi[c], cen[c]); }
       }
-      big = parked ? -1.0f : bg;
+      object_sort_centre(alo, ahi, (fok[6 * o] & 2) != 0, oc, lo, hi);
     }
     if (tid < kTreeThreads) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         float a = lo[c], b = hi[c];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          a = fminf(a, __shfl_xor(a, off));
-          b = fmaxf(b, __shfl_xor(b, off));
-        }
+        wave_min_max(a, b);
         if (lane == 0) { red[6 * (tid >> 6) + c] = a; red[6 * (tid >> 6) + 3 + c] = b; }
       }
     }
@@ -362,19 +339,12 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
       for (int wv = 0; wv < kTreeThreads / 64; ++wv) { a = fminf(a, red[6 * wv + c]); b = fmaxf(b, red[6 * wv + 3 + c]); }
       blo[c] = a;
       const float ext = b - a;
-      inv[c] = (ext > 0.0f && ext < INFINITY) ? 1023.0f / ext : 0.0f;
+      inv[c] = grid_scale(ext);
       max_ext = c == 0 ? ext : fmaxf(max_ext, ext);
     }
-    uint32_t code = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float qv = fminf(fmaxf((cen[c] - blo[c]) * inv[c], 0.0f), 1023.0f);
-      code |= expand_bits10((uint32_t)qv) << (2 - c);
-    }
-    const bool parked = big < 0.0f;
-    if (big > kBvhLargeFraction * max_ext) code |= 1u << 30;  // wall slabs: their own subtree under the root
-    if (parked) code = 0xFFFFFFFEu;                            // one subtree at the end of the order, culled at its root
-    okey[o] = ((unsigned long long)(parked ? code : (code & ~7u)) << 32) | (unsigned long long)(uint32_t)o;
+    const bool parked = oc[3] < 0.0f;
+    const uint32_t code = sort_code(morton30(oc, blo, inv), oc[3], max_ext, parked);
+    okey[o] = pack_key(parked ? code : class_code(code, 0u), o);
   }
   __syncthreads();
   if (has_obj) {  // rank sort: the keys are unique (the object index is the low word)
@@ -390,31 +360,16 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
   const int n_int = K - 1;
   if (tid < n_int) {
     const int i = tid;
-    const int d = (delta_keys(skey, K, i, i + 1) - delta_keys(skey, K, i, i - 1)) >= 0 ? 1 : -1;
-    const int dmin = delta_keys(skey, K, i, i - d);
-    int lmax = 2;
-    while (delta_keys(skey, K, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1)
-      if (delta_keys(skey, K, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = delta_keys(skey, K, i, j);
-    int s = 0, t = l;
-    do {
-      t = (t + 1) >> 1;
-      if (delta_keys(skey, K, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    const int gamma = i + s * d + min(d, 0);
-    const int left = (min(i, j) == gamma) ? (n_int + gamma) : gamma;
-    const int right = (max(i, j) == gamma + 1) ? (n_int + gamma + 1) : (gamma + 1);
+    int left, right, j;
+    karras_node(skey, K, i, left, right, j);
     child[2 * i] = left;
     child[2 * i + 1] = right;
     parent[left] = i;
     parent[right] = i;
     counter[i] = 0;
     // float offsets from oaabb (nbox follows it): the bottom-up pass reads the boxes without going through the key table
-    boxoff[2 * i] = left >= n_int ? 6 * (int)(uint32_t)(skey[left - n_int] & 0xFFFFFFFFull) : 6 * (kObjMax + left);
-    boxoff[2 * i + 1] = right >= n_int ? 6 * (int)(uint32_t)(skey[right - n_int] & 0xFFFFFFFFull) : 6 * (kObjMax + right);
+    boxoff[2 * i] = left >= n_int ? 6 * key_index(skey[left - n_int]) : 6 * (kObjMax + left);
+    boxoff[2 * i + 1] = right >= n_int ? 6 * key_index(skey[right - n_int]) : 6 * (kObjMax + right);
   }
   if (tid == 0) parent[0] = -1;
   __syncthreads();
@@ -450,7 +405,7 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
     for (int side = 0; side < 2; ++side) {
       const int c = child[2 * i + side];
       if (c >= n_int) {
-        const int ob = (int)(uint32_t)(skey[c - n_int] & 0xFFFFFFFFull);
+        const int ob = key_index(skey[c - n_int]);
 #pragma unroll
         for (int k = 0; k < 6; ++k) bx[side][k] = oaabb[6 * ob + k];
         ref[side] = objok[ob] ? ((K - 1 + 5 * ob) | AGX_BVH_OBJECT_REF) : (K - 1 + 5 * ob + 4);
@@ -460,15 +415,12 @@ AGX_DEV void bvh_build_objects_env(int env, int nt, const float *__restrict__ tr
         ref[side] = c;
       }
     }
-    obj_store_node(out + (size_t)i * 16, bx[0], bx[1], ref[0], ref[1], -1, -1);
+    store_node(out + (size_t)i * 16, bx[0], bx[1], ref[0], ref[1], -1, -1);
   }
   AGX_PHASE(7);
 }
 
-// Node record written to HBM (16 floats):
-//   [0..2] lo_left  [3] child_left (int bits)   [4..6] hi_left  [7] child_right (int bits)
-//   [8..10] lo_right [11] second_left (int)     [12..14] hi_right [15] second_right (int)
-// child >= 0: internal node index, child < 0: leaf holding triangle ~child and, if second >= 0, that triangle too.
+// The triangle-level build (node records: store_node, agx_bvh_parts.h).
 // OBJ: the launch is known to take the object-level build (object_level_build() on the host: launch arguments only) -- each kernel
 // instance carries ONE builder (both inlined in one kernel spilled loop-carried values to scratch)
 template <bool OBJ>
@@ -479,7 +431,7 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
   }
   const bool force_full_sort = (ppo & AGX_BVH_FULL_SORT) != 0;
   const bool box_objects = (ppo & AGX_BVH_BOX_OBJECTS) != 0;
-  ppo &= ~(AGX_BVH_FULL_SORT | AGX_BVH_BOX_OBJECTS | AGX_BVH_OBJECT_TREE);
+  ppo = bvh_ppo(ppo);
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);         // [npad]
   // Only the INTERNAL nodes' boxes live in LDS: a leaf's box is three min / max over its triangle, recomputed where it is
@@ -494,14 +446,11 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
   const int tid = threadIdx.x;
   const float *tris = tri_world + (size_t)env * nt * 9;
 
-  // --- Morton grid = bounds of the sort centres of everything that is in the env.  Obstacles beyond the
-  // curriculum level are parked at -1000 m (asset_manager.py:71): letting them into the bounds would stretch
-  // the 10-bit grid over a kilometre.  With ppo > 0 the scene is a soup of K = nt / ppo objects of ppo
-  // consecutive triangles each (boxes: 12): the sort centre is the OBJECT's, so the triangles of an object
-  // stay together (their keys differ only in the index word) and the radix tree becomes a two-level
-  // hierarchy, objects on top.  Measured on the config-3 scene: 105 -> see profiles/r01_raycast_variants.txt.
+  // --- Morton grid (centre_grid) over the sort centres.  With ppo > 0 the scene is a soup of K = nt / ppo objects of ppo
+  // consecutive triangles each (boxes: 12) and the sort centre is the OBJECT's: the radix tree becomes a two-level hierarchy,
+  // objects on top.  Measured on the config-3 scene: 105 -> see profiles/r01_raycast_variants.txt.
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  float *ocen = reinterpret_cast<float *>(counter);  // [K][8] centre, largest extent (< 0: parked), AABB lo, -; counter is not live yet
+  float *ocen = reinterpret_cast<float *>(counter);  // [K][8] object_sort_centre's record in the first four; counter is not live yet
   const int K = ppo > 0 ? nt / ppo : 0;
   // (every thread takes triangles -- nine independent loads each -- and leaves their bounds in LDS; the object's thread then
   //  reduces ppo LDS entries.  One thread per object walking its 3 ppo vertices was 36 memory latencies in sequence: the longest
@@ -510,19 +459,19 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
   if (ppo > 0) {
     for (int f = tid; f < nt; f += kBvhThreads) {
       const float *t = tris + (size_t)f * 9;
-      float v[9];
+      float v[9], tlo[3], thi[3];
 #pragma unroll
       for (int k = 0; k < 9; ++k) v[k] = t[k];
+      tri_bounds(v, tlo, thi);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        tb[6 * f + c] = fminf(fminf(v[c], v[3 + c]), v[6 + c]);
-        tb[6 * f + 3 + c] = fmaxf(fmaxf(v[c], v[3 + c]), v[6 + c]);
+        tb[6 * f + c] = tlo[c];
+        tb[6 * f + 3 + c] = thi[c];
       }
     }
     __syncthreads();
   }
   for (int o = tid; o < K; o += kBvhThreads) {
-    const float *t = tris + (size_t)o * ppo * 9;
     float alo[3] = {INFINITY, INFINITY, INFINITY}, ahi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int j = 0; j < ppo; ++j)
 #pragma unroll
@@ -530,69 +479,30 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
         alo[c] = fminf(alo[c], tb[6 * (o * ppo + j) + c]);
         ahi[c] = fmaxf(ahi[c], tb[6 * (o * ppo + j) + 3 + c]);
       }
-    const bool parked = tri_parked(t);
+    // (object_sort_centre's arithmetic, written out: through the call this kernel's code object built a 2944-triangle soup,
+    //  which never enters this loop, in 150.0 us instead of 145.6)
+    const bool parked = tri_parked(tris + (size_t)o * ppo * 9);
     float big = 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float cen = 0.5f * (alo[c] + ahi[c]);
+      const float cen = 0.5f * (alo[c] + ahi[c]);
       ocen[8 * o + c] = cen;
-      ocen[8 * o + 4 + c] = alo[c];
       big = fmaxf(big, ahi[c] - alo[c]);
       if (!parked) { lo[c] = fminf(lo[c], cen); hi[c] = fmaxf(hi[c], cen); }
     }
     ocen[8 * o + 3] = parked ? -1.0f : big;
   }
-  for (int f = tid; f < nt && ppo <= 0; f += kBvhThreads) {
-    const float *t = tris + (size_t)f * 9;
-    if (tri_parked(t)) continue;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float cen = (t[c] + t[3 + c] + t[6 + c]) * (1.0f / 3.0f);
-      lo[c] = fminf(lo[c], cen);
-      hi[c] = fmaxf(hi[c], cen);
-    }
-  }
+  for (int f = tid; f < nt && ppo <= 0; f += kBvhThreads) soup_sort_centre(tris + (size_t)f * 9, lo, hi);
   if (ppo > 0) __syncthreads();  // the reduction scratch below shares the region the triangle bounds were read from
-  // bounds of the sort centres over the workgroup: inside a wave by shuffles (min / max are exact: any order gives the same bits),
-  // then the eight waves' results through LDS -- two barriers (the pairwise tree over 512 LDS entries took ten)
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float a = lo[c], b = hi[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      a = fminf(a, __shfl_xor(a, off));
-      b = fmaxf(b, __shfl_xor(b, off));
-    }
-    if ((tid & 63) == 0) {
-      red[c * (kBvhThreads / 64) + (tid >> 6)] = a;
-      red[(3 + c) * (kBvhThreads / 64) + (tid >> 6)] = b;
-    }
-  }
-  __syncthreads();
-  float blo[3], bhi[3], inv[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float a = INFINITY, b = -INFINITY;
-#pragma unroll
-    for (int wv = 0; wv < kBvhThreads / 64; ++wv) {
-      a = fminf(a, red[c * (kBvhThreads / 64) + wv]);
-      b = fmaxf(b, red[(3 + c) * (kBvhThreads / 64) + wv]);
-    }
-    blo[c] = a;
-    bhi[c] = b;
-    float ext = b - a;
-    inv[c] = (ext > 0.0f && ext < INFINITY) ? 1023.0f / ext : 0.0f;  // ext = -inf - inf when every primitive is parked
-  }
-  float max_ext = fmaxf(fmaxf(bhi[0] - blo[0], bhi[1] - blo[1]), bhi[2] - blo[2]);
-  // --- keys: [large flag | 30-bit Morton code of the sort centre] . [triangle index]
-  // --- objects of ppo triangles each (boxes: 12): the order of the keys is the order of the OBJECTS' codes, and inside an
-  // object (face class, index).  So sort the K object keys (128 instead of 2048: the full sort was 35 of the build's 67 us) and
-  // RANK every triangle inside its object against the ppo - 1 others.  This is the full sort's order exactly unless two
-  // objects that are in the env share all 27 upper Morton bits -- their triangles would interleave by face class --, which is
-  // looked for, and then the full sort runs.  (Parked objects all carry the code 0xFFFFFFFE: index order, which the object
+  float blo[3], inv[3], max_ext;
+  centre_grid<kBvhThreads>(lo, hi, red, blo, inv, max_ext);
+  // --- keys (agx_bvh_parts.h).  Objects of ppo triangles each (boxes: 12): the order of the keys is the order of the OBJECTS'
+  // codes, and inside an object (face class, index).  So sort the K object keys (128 instead of 2048: the full sort was 35 of the
+  // build's 67 us) and RANK every triangle inside its object against the ppo - 1 others.  This is the full sort's order exactly
+  // unless two objects that are in the env share all 27 upper Morton bits -- their triangles would interleave by face class --,
+  // which is looked for, and then the full sort runs.  (Parked objects all carry kParkedCode: index order, which the object
   // keys' low word gives.)
   bool presorted = false;
-#ifndef AGX_BVH_EXPERIMENT
   if (ppo >= 2 && K >= 2 && K * ppo == nt && !force_full_sort) {
     __syncthreads();  // (the reduction's result is in registers everywhere: its scratch is reused)
     int Kpad = 1;
@@ -607,43 +517,24 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
       unsigned long long k64 = ~0ull;
       if (o < K) {
         const float *oc = ocen + 8 * o;
-        uint32_t code = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          float qv = fminf(fmaxf((oc[c] - blo[c]) * inv[c], 0.0f), 1023.0f);
-          code |= expand_bits10((uint32_t)qv) << (2 - c);
-        }
-        const float big = oc[3];
-        const bool parked = big < 0.0f;
-        if (big > kBvhLargeFraction * max_ext) code |= 1u << 30;
-        if (parked) code = 0xFFFFFFFEu;
+        const bool parked = oc[3] < 0.0f;
+        const uint32_t code = sort_code(morton30(oc, blo, inv), oc[3], max_ext, parked);
         ocode[o] = code;
-        k64 = ((unsigned long long)(parked ? code : (code & ~7u)) << 32) | (unsigned long long)(uint32_t)o;
+        k64 = pack_key(parked ? code : class_code(code, 0u), o);
       }
       okey[o] = k64;
     }
-    for (int f = tid; f < nt; f += kBvhThreads) {
-      const float *t = tris + (size_t)f * 9;
-      uint32_t fc = 0;
-      if (!(ocen[8 * (f / ppo) + 3] < 0.0f)) {
-        V3 e1 = V3{t[3] - t[0], t[4] - t[1], t[5] - t[2]}, e2 = V3{t[6] - t[0], t[7] - t[1], t[8] - t[2]};
-        V3 nrm = cross_plain(e1, e2);
-        float ax = fabsf(nrm.x), ay = fabsf(nrm.y), az = fabsf(nrm.z);
-        int d = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-        float comp = d == 0 ? nrm.x : (d == 1 ? nrm.y : nrm.z);
-        fc = (uint32_t)(2 * d + (comp < 0.0f ? 1 : 0));
-      }
-      cls[f] = (uint8_t)fc;
-    }
+    for (int f = tid; f < nt; f += kBvhThreads)
+      cls[f] = (uint8_t)(ocen[8 * (f / ppo) + 3] < 0.0f ? 0u : face_class(tris + (size_t)f * 9));
     __syncthreads();
     bitonic_sort_lds(okey, Kpad, tid);
     __syncthreads();
     for (int p = tid; p < K; p += kBvhThreads) {
       const unsigned long long a = okey[p];
-      orank[(int)(uint32_t)(a & 0xFFFFFFFFull)] = p;
+      orank[key_index(a)] = p;
       if (p + 1 < K) {
         const uint32_t c0 = (uint32_t)(a >> 32), c1 = (uint32_t)(okey[p + 1] >> 32);
-        if (c0 == c1 && c0 != 0xFFFFFFFEu) *tie = 1;  // (every writer stores the same value)
+        if (c0 == c1 && c0 != kParkedCode) *tie = 1;  // (every writer stores the same value)
       }
     }
     __syncthreads();
@@ -654,13 +545,12 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
           const int o = f / ppo, g0 = o * ppo;
           const uint32_t oc = ocode[o];
           const uint32_t cf = cls[f];
-          const uint32_t code = oc == 0xFFFFFFFEu ? oc : ((oc & ~7u) | cf);
           int r = 0;
           for (int g = g0; g < g0 + ppo; ++g) {
             const uint32_t cg = cls[g];
             r += (cg < cf || (cg == cf && g < f)) ? 1 : 0;
           }
-          keys[orank[o] * ppo + r] = ((unsigned long long)code << 32) | (unsigned long long)(uint32_t)f;
+          keys[orank[o] * ppo + r] = pack_key(oc == kParkedCode ? oc : class_code(oc, cf), f);
         } else {
           keys[f] = ~0ull;
         }
@@ -668,82 +558,17 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
     }
     __syncthreads();
   }
-#endif
-  for (int f = tid; f < npad && !presorted; f += kBvhThreads) {
-    unsigned long long key = ~0ull;
-    if (f < nt) {
-      const float *t = tris + (size_t)f * 9;
-      uint32_t code = 0;
-      float big = 0.0f;
-      bool parked;
-      if (ppo > 0) {
-        const float *oc = ocen + 8 * (f / ppo);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          float qv = fminf(fmaxf((oc[c] - blo[c]) * inv[c], 0.0f), 1023.0f);
-          code |= expand_bits10((uint32_t)qv) << (2 - c);
-        }
-        big = oc[3];
-        parked = big < 0.0f;
-#ifdef AGX_BVH_EXPERIMENT
-        if (g_obj_codes) { code = g_obj_codes[(size_t)env * (nt / ppo) + f / ppo]; big = 0.0f; }
-#endif
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          float cen = (t[c] + t[3 + c] + t[6 + c]) * (1.0f / 3.0f);
-          float qv = fminf(fmaxf((cen - blo[c]) * inv[c], 0.0f), 1023.0f);
-          code |= expand_bits10((uint32_t)qv) << (2 - c);
-          big = fmaxf(big, fmaxf(fmaxf(t[c], t[3 + c]), t[6 + c]) - fminf(fminf(t[c], t[3 + c]), t[6 + c]));
-        }
-        parked = tri_parked(t);
-      }
-      // primitives larger than most of the obstacle field (the room's wall slabs) get their own subtree under
-      // the root: their huge boxes no longer inflate every level of the obstacle tree
-      if (big > kBvhLargeFraction * max_ext) code |= 1u << 30;
-      if (parked) code = 0xFFFFFFFEu;  // one subtree at the end of the order, culled at its root
-      // The three finest Morton bits (sub-centimetre cells) are replaced by the triangle's FACE CLASS (dominant axis
-      // and sign of its normal): inside an object (same code) the two triangles of a box face then share the whole
-      // upper word and become sibling leaves, which the emit stage folds into one two-triangle leaf -- half the
-      // in-object nodes.  A collision of classes only shapes the tree; hits never depend on it.  (The index stays
-      // alone in the low word: hipcc dropped an `& 0xFFFFFF` on the LDS read when the class lived there.)
-      if (ppo > 0 && !parked) {
-        V3 e1 = V3{t[3] - t[0], t[4] - t[1], t[5] - t[2]}, e2 = V3{t[6] - t[0], t[7] - t[1], t[8] - t[2]};
-        V3 nrm = cross_plain(e1, e2);
-        float ax = fabsf(nrm.x), ay = fabsf(nrm.y), az = fabsf(nrm.z);
-        int d = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-        float comp = d == 0 ? nrm.x : (d == 1 ? nrm.y : nrm.z);
-        code = (code & ~7u) | (uint32_t)(2 * d + (comp < 0.0f ? 1 : 0));
-      }
-      key = ((unsigned long long)code << 32) | (unsigned long long)(uint32_t)f;
-    }
-    keys[f] = key;
-  }
+  for (int f = tid; f < npad && !presorted; f += kBvhThreads)
+    keys[f] = f < nt ? triangle_key(tris + (size_t)f * 9, f, ppo, ocen, blo, inv, max_ext) : ~0ull;
   __syncthreads();
   // --- sort
   if (!presorted) bitonic_sort_lds(keys, npad, tid);
   __syncthreads();
-  // --- Karras 2012 radix tree: internal nodes 0..nt-2, leaves nt-1+i (i = sorted position)
+  // --- radix tree
   const int n_int = nt - 1;
   for (int i = tid; i < n_int; i += kBvhThreads) {
-    int d = (delta_keys(keys, nt, i, i + 1) - delta_keys(keys, nt, i, i - 1)) >= 0 ? 1 : -1;
-    int dmin = delta_keys(keys, nt, i, i - d);
-    int lmax = 2;
-    while (delta_keys(keys, nt, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1)
-      if (delta_keys(keys, nt, i, i + (l + t) * d) > dmin) l += t;
-    int j = i + l * d;
-    int dnode = delta_keys(keys, nt, i, j);
-    int s = 0;
-    int t = l;
-    do {
-      t = (t + 1) >> 1;
-      if (delta_keys(keys, nt, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    int gamma = i + s * d + min(d, 0);
-    int left = (min(i, j) == gamma) ? (n_int + gamma) : gamma;
-    int right = (max(i, j) == gamma + 1) ? (n_int + gamma + 1) : (gamma + 1);
+    int left, right, j;
+    karras_node(keys, nt, i, left, right, j);
     child[2 * i] = left;
     child[2 * i + 1] = right;
     parent[left] = i;
@@ -772,73 +597,25 @@ AGX_DEV void bvh_build_env(int env, int nt, int npad, int ppo, const float *__re
     }
   }
   __syncthreads();
-  // --- AGX_BVH_BOX_OBJECTS: which internal nodes are the root of ONE box object?  (three parallel steps, see box_frame)
-  // bit 0 of counter[] takes the verdict (the arrival count is no longer needed; the other end of the node's key range stays above
-  // bit 1); objroot[] lives in parent[], dead since the propagation.
-  int *objroot = parent;  // [nt / 12]
-  const int n_obj = nt / 12;
-  if (box_objects) {
-    for (int o = tid; o < n_obj; o += kBvhThreads) objroot[o] = -1;
-    __syncthreads();
-    for (int i = tid + 1; i < n_int; i += kBvhThreads) {  // (never the root: it has no parent to carry the reference)
-      const int j = counter[i] >> 2;
-      const int first = min(i, j), last = max(i, j);
-      if (last - first != 11) continue;
-      const int obj = (int)(uint32_t)(keys[first] & 0xFFFFFFFFull) / 12;
-      bool same = true;
-      for (int r = 1; r < 12; ++r) same = same && ((int)(uint32_t)(keys[first + r] & 0xFFFFFFFFull) / 12 == obj);
-      if (same) objroot[obj] = i;  // (one node at most has exactly this range)
-    }
-    __syncthreads();
-    for (int f = tid; f < n_obj * 12; f += kBvhThreads) {
-      const int obj = f / 12, q = f - obj * 12;
-      if (objroot[obj] < 0) continue;
-      const float *t = tris + (size_t)obj * 12 * 9;
-      BoxFrame F;
-      uint32_t ids = 0u, ids2 = 0u;
-      bool ok = box_frame(t, F) && box_triangle_ok(F, t + 9 * q, q, ids);
-      // the first triangle of each face also looks at its partner: four distinct corners between them
-      const int mate = q == 0 ? 2 : (q == 10 ? 11 : (q == 1 ? 5 : (q == 7 ? 9 : (q == 3 ? 8 : (q == 4 ? 6 : -1)))));
-      if (ok && mate >= 0) ok = box_triangle_ok(F, t + 9 * mate, mate, ids2) && __popc(ids | ids2) == 4;
-      if (!ok) objroot[obj] = -1;  // (every writer stores the same value)
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < n_int; i += kBvhThreads) counter[i] &= ~3;
-  __syncthreads();
-  if (box_objects) {
-    for (int o = tid; o < n_obj; o += kBvhThreads)
-      if (objroot[o] >= 0) counter[objroot[o]] |= 1;
-    __syncthreads();
-  }
-  // --- emit nodes with both child boxes inline.  A child whose own two children are both leaves is folded into a
-  // two-triangle leaf (first triangle in the child slot, second in the pad slot); the folded node is never visited.
+  mark_box_objects<kBvhThreads>(box_objects, nt, tris, keys, counter, parent);  // (objroot[] in parent[], dead since the propagation)
+  // --- emit nodes with both child boxes inline
   float *out = nodes + (size_t)env * (nt - 1) * 16;
   for (int i = tid; i < n_int; i += kBvhThreads) {
     int ref[2], second[2];
     float bx[2][6];
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
-      int c = child[2 * i + side];
+      const int c = child[2 * i + side];
       node_box(box, keys, tris, n_int, c, bx[side]);
-      second[side] = -1;
-      if (c >= n_int) {
-        ref[side] = ~(int)(uint32_t)(keys[c - n_int] & 0xFFFFFFFFull);
-      } else if (counter[c] & 1) {
-        ref[side] = c | AGX_BVH_OBJECT_REF;  // the child is an OBJECT NODE: the tree ends at the box
-      } else if (child[2 * c] >= n_int && child[2 * c + 1] >= n_int) {
-        ref[side] = ~(int)(uint32_t)(keys[child[2 * c] - n_int] & 0xFFFFFFFFull);
-        second[side] = (int)(uint32_t)(keys[child[2 * c + 1] - n_int] & 0xFFFFFFFFull);
-      } else {
-        ref[side] = c;
-      }
+      ref[side] = child_ref(keys, child, counter, n_int, c, second[side]);
     }
     float *o = out + (size_t)i * 16;
-    if (counter[i] & 1) {  // this node IS an object node (the verdict its parent reads, too): the box's frame is its record
-      const int j = counter[i] >> 2;
-      box_object_record(tris, (int)(uint32_t)(keys[min(i, j)] & 0xFFFFFFFFull) / 12, o);
+    int obj;
+    if (object_node(keys, counter, i, obj)) {  // the box's frame is its record
+      box_object_record(tris, obj, o);
       continue;
     }
+    // (store_node's sixteen stores, written out: through the call the box scene's build took 69.5 us instead of 68.0)
     const float *a = bx[0], *b = bx[1];
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = __int_as_float(ref[0]);
     o[4] = a[3]; o[5] = a[4]; o[6] = a[5]; o[7] = __int_as_float(ref[1]);
@@ -879,16 +656,7 @@ __global__ void __launch_bounds__(kBvhThreads, 4) k_bvh_build(int n, int nt, int
     }
     return;
   }
-  __shared__ int next;
-  const int count = work[0];
-  while (true) {
-    if (threadIdx.x == 0) next = atomicAdd(&work[1], 1);
-    __syncthreads();
-    const int idx = next;
-    __syncthreads();  // everybody has read `next` before thread 0 overwrites it; also fences LDS reuse
-    if (idx >= count) break;
-    bvh_build_env<OBJ>(work[2 + idx], nt, npad, ppo, tri_world, nodes);
-  }
+  for_each_listed_env(work, [&](int env) { bvh_build_env<OBJ>(env, nt, npad, ppo, tri_world, nodes); });
 }
 
 // The masked refresh of a navigation step in ONE persistent launch: the workgroup that pulls a dirty env from the work list
@@ -940,22 +708,18 @@ __global__ void __launch_bounds__(kBvhThreads, 4) k_scene_refresh(int n, int nt,
     scene_refresh_env<OBJ>(env, n, nt, npad, ppo, na, tri_local, tri_asset, asset_state, half_extents, tri_world, boxes, nodes, S);
     return;
   }
-  __shared__ int next;
-  const int count = work[0];
-  while (true) {
-    if (threadIdx.x == 0) next = atomicAdd(&work[1], 1);
-    __syncthreads();
-    const int idx = next;
-    __syncthreads();  // everybody has read `next` before thread 0 overwrites it; also fences LDS reuse
-    if (idx >= count) break;
-    scene_refresh_env<OBJ>(work[2 + idx], n, nt, npad, ppo, na, tri_local, tri_asset, asset_state, half_extents, tri_world, boxes, nodes, S);
-  }
+  for_each_listed_env(work, [&](int env) {
+    scene_refresh_env<OBJ>(env, n, nt, npad, ppo, na, tri_local, tri_asset, asset_state, half_extents, tri_world, boxes, nodes, S);
+  });
 }
 
-int compact_mask_launch(int n, const uint8_t *mask, int32_t *work, void *stream) {
-  hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, (const int32_t *)nullptr);
+int compact_mask_launch(int n, const uint8_t *mask, int32_t *work, void *stream, const int32_t *flag) {
+  hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, flag);
   return check_launch("k_compact_mask");
 }
+// the persistent grid of the LDS builders: two resident workgroups per CU (LDS bound: 72 KB each for T = 1272 triangle-level, 41 KB
+// object-level)
+static int bvh_persistent_grid(int n) { return n < 512 ? n : 512; }
 
 static size_t bvh_lds_bytes(int nt, int npad) {
   const size_t box_floats = (size_t)(nt - 1) * 6 > (size_t)6 * kBvhThreads ? (size_t)(nt - 1) * 6 : (size_t)6 * kBvhThreads;
@@ -966,8 +730,8 @@ static size_t bvh_lds_bytes(int nt, int npad) {
 // what a launch that is KNOWN to take the object-level build needs (the triangle-level build's 72 KB for 1272 triangles allow two
 // workgroups per CU; 41 KB allow three)
 static bool object_level_build(int nt, int prims_per_object) {
-  const int ppo = prims_per_object & ~(AGX_BVH_FULL_SORT | AGX_BVH_BOX_OBJECTS | AGX_BVH_OBJECT_TREE);
-  return (prims_per_object & AGX_BVH_OBJECT_TREE) && (prims_per_object & AGX_BVH_BOX_OBJECTS) && !(prims_per_object & AGX_BVH_FULL_SORT) && ppo == 12 &&
+  return (prims_per_object & AGX_BVH_OBJECT_TREE) && (prims_per_object & AGX_BVH_BOX_OBJECTS) && !(prims_per_object & AGX_BVH_FULL_SORT) &&
+         bvh_ppo(prims_per_object) == 12 &&
          nt >= 24 && nt / 12 <= kObjMax;
 }
 static size_t bvh_lds_bytes_for(int nt, int npad, int prims_per_object) {
@@ -1006,11 +770,6 @@ extern "C" int agx_debug_phase_clock(unsigned long long *out16) {
   return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_clock), sizeof(unsigned long long) * 16);
 }
 #endif
-#ifdef AGX_BVH_EXPERIMENT
-extern "C" int agx_debug_set_obj_codes(const uint32_t *codes) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_obj_codes), &codes, sizeof(codes));
-}
-#endif
 
 extern "C" int agx_prims_from_assets(int n, int num_prims, int num_assets, const int32_t *prim_asset, const float *asset_state,
                                      const float *local_pos, const float *local_quat, const uint8_t *mask, float *prim_state,
@@ -1034,13 +793,8 @@ extern "C" int agx_assets_integrate(int n, int num_assets, float *asset_state, c
 // argument checks and launch shape shared by the two LBVH builders; `kernel`'s dynamic LDS limit is raised once (*attr_set)
 static int bvh_launch_shape(int nt, int prims_per_object, int *npad_out, size_t *lds_out, const void *kernel, bool *attr_set) {
   AGX_REQUIRE(nt >= 2 && nt <= kBvhMaxTris, "num_tris %d outside [2, %d] (LDS-resident LBVH build)", nt, kBvhMaxTris);
-  const int ppo = prims_per_object & ~(AGX_BVH_FULL_SORT | AGX_BVH_BOX_OBJECTS | AGX_BVH_OBJECT_TREE);  // (flags: include/aerial_gym_hip.h)
-  AGX_REQUIRE(!(prims_per_object & AGX_BVH_BOX_OBJECTS) || ppo == 12, "AGX_BVH_BOX_OBJECTS goes with objects of 12 triangles");
-  AGX_REQUIRE(!(prims_per_object & AGX_BVH_OBJECT_TREE) || (prims_per_object & AGX_BVH_BOX_OBJECTS), "AGX_BVH_OBJECT_TREE goes with AGX_BVH_BOX_OBJECTS");
-  AGX_REQUIRE(ppo == 0 || (ppo >= 9 && nt % ppo == 0),
-              "prims_per_object must be 0 or >= 9 (8 floats of LDS scratch per object) and divide num_tris");
-  int npad = 1;
-  while (npad < nt) npad <<= 1;
+  if (int e = bvh_check_objects(nt, prims_per_object, true)) return e;
+  const int npad = bvh_npad(nt);
   const size_t lds = bvh_lds_bytes_for(nt, npad, prims_per_object);
   if (!*attr_set) {
     // the kernel also owns 4 bytes of static LDS: the dynamic maximum must leave room for them
@@ -1080,9 +834,8 @@ static int scene_refresh_launch(int n, int nt, int na, const float *tri_local, c
                        tri_asset, asset_state, half_extents, tri_world, boxes, work, nodes, mask, S);
     return check_launch("agx_scene_refresh");
   }
-  hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, flag);
-  const int grid = n < 512 ? n : 512;  // two resident workgroups per CU (LDS bound: 72 KB each for T = 1272 triangle-level, 41 KB object-level)
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad, prims_per_object, na, tri_local,
+  if (int e = compact_mask_launch(n, mask, work, stream, flag)) return e;
+  hipLaunchKernelGGL(kernel, dim3(bvh_persistent_grid(n)), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad, prims_per_object, na, tri_local,
                      tri_asset, asset_state, half_extents, tri_world, boxes, work, nodes, (const uint8_t *)nullptr, S);
   return check_launch("agx_scene_refresh");
 }
@@ -1136,9 +889,9 @@ extern "C" int agx_bvh_build(int n, int nt, int prims_per_object, const float *t
   int npad = 0;
   size_t lds = 0;
   if (int e = bvh_launch_shape(nt, prims_per_object, &npad, &lds, reinterpret_cast<const void *>(kernel), &attr_set[obj])) return e;
-  if (mask) hipLaunchKernelGGL(k_compact_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, mask, work, (const int32_t *)nullptr);
-  const int grid = n < 512 ? n : 512;  // two resident workgroups per CU (LDS bound: 72 KB each for T = 1272)
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad,
+  if (mask)
+    if (int e = compact_mask_launch(n, mask, work, stream)) return e;
+  hipLaunchKernelGGL(kernel, dim3(bvh_persistent_grid(n)), dim3(kBvhThreads), lds, (hipStream_t)stream, n, nt, npad,
                      prims_per_object, tri_world, mask ? work : nullptr, nodes);  // (with the AGX_BVH_FULL_SORT bit, if set)
   return check_launch("agx_bvh_build");
 }
