@@ -298,7 +298,15 @@ class AgxComOffset(C.Structure):
     _fields_ = [("c", C.c_float * 3), ("reserved", C.c_float)]
 
 
-ABI_VERSION = 21  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+class AgxVaeConv(C.Structure):
+    """one convolution of the VAE encoder (agx_vae_conv2d)"""
+    _fields_ = [(k, C.c_int32) for k in ("cin", "cout", "kh", "kw", "stride", "pad_h", "pad_w", "in_h", "in_w", "out_h", "out_w",
+                                          "src_h", "src_w")]
+
+
+VAE_ELU, VAE_LAYERS, MATH_EXPM1 = 1, 11, 5  # AGX_VAE_ELU, AGX_VAE_LAYERS, AGX_MATH_EXPM1
+
+ABI_VERSION = 22  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -438,6 +446,22 @@ _SIGNATURES = {
         [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.c_float, _P, _P, C.c_int, C.c_int, _P, _P],
     ),
     "agx_obs_lidar_navigation": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    # VAE depth-image encoder (csrc/agx_vae.hip)
+    "agx_vae_packed_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "agx_vae_pack_weight": (C.c_int, [C.c_int, C.c_int, _P, _P]),
+    "agx_vae_unpack_weight": (C.c_int, [C.c_int, C.c_int, _P, _P]),
+    "agx_vae_conv2d": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.POINTER(AgxVaeConv), C.c_int, _P, _P, _P]),
+    "agx_vae_linear": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "agx_vae_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "agx_vae_sample": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_uint64, C.c_int, C.c_int, _P]),
+    "agx_vae_noise": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.c_int, _P, _P]),
+    "agx_vae_place_latents": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "agx_vae_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "agx_vae_destroy": (C.c_int, [_P]),
+    "agx_vae_workspace_bytes": (C.c_size_t, [_P, C.c_int]),
+    "agx_vae_envs_per_chunk": (C.c_int, [_P, C.c_size_t, C.c_int]),
+    "agx_vae_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
+    "agx_vae_layer_info": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -1,5 +1,9 @@
 """Task configs (aerial_gym/config/task_config/{position_setpoint,navigation}_task_config.py)."""
+import os
+
 import torch
+
+_PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class position_setpoint_task_config:
@@ -93,8 +97,8 @@ class navigation_task_config:
     use_warp = True
     headless = True
     device = "cuda:0"
-    # the reference packs 13 + 4 state/action entries + 64 VAE latents; the VAE encoder is a
-    # dense conv net outside the simulation hot path, so `use_vae = False` gives 17 + pooled depth
+    # the reference packs 13 + 4 state/action entries + 64 VAE latents (vae_config.use_vae = True: the encoder of
+    # utils/vae); `use_vae = False` gives 17 + pooled depth
     observation_space_dim = 13 + 4 + 64
     privileged_observation_space_dim = 0
     action_space_dim = 4
@@ -126,8 +130,13 @@ class navigation_task_config:
     REWARD_PARAMETER_ORDER = tuple(reward_parameters.keys())
 
     class vae_config:
+        # False (default here; the reference: True): a min-pooled 8x8 depth grid takes the latents' place.  True: the
+        # reference's encoder on HIP kernels (utils/vae/vae_image_encoder.py) with the weights named below.
         use_vae = False
-        latent_dims = 64  # min-pooled 8x8 depth grid takes the latents' place (see navigation_task.py here)
+        latent_dims = 64
+        # the reference's trained weights (aerial_gym/utils/vae/weights/ upstream): not shipped here, copy the file there
+        model_file = "ICRA_test_set_more_sim_data_kld_beta_3_LD_64_epoch_49.pth"
+        model_folder = os.path.join(_PKG_DIR, "utils", "vae", "weights")
         image_res = (270, 480)
         interpolation_mode = "nearest"
         return_sampled_latent = True

@@ -235,6 +235,33 @@ AGX_DEV float exp_cw(float x) {
   const double two_k = __longlong_as_double((long long)(k + 1023) << 52);  // 2^k, -126 <= k <= 128
   return (float)(e * two_k);
 }
+// expm1 (the negative branch of ELU, where torch evaluates expm1): exp_cw's reduction x = k ln2 + r and polynomial,
+// e^r - 1 = q = r + r^2 p(r).  k = 0 (|x| < ln2 / 2) returns q itself: nothing cancels near zero, tiny arguments come
+// back as they are.  Otherwise 2^k q + (2^k - 1), whose terms do not cancel because |e^x - 1| > 0.29 there.
+// Below -104, e^x is far under half an ulp of 1: -1.
+AGX_DEV float expm1_cw(float x) {
+  if (x > 88.7228317f) return INFINITY;
+  if (x < -104.0f) return -1.0f;
+  if (x == 0.0f) return x;  // (-0 stays -0: the sums below would turn it into +0)
+  const double xd = (double)x;
+  const double kd = __builtin_rint(xd * kInvLn2);
+  const int k = (int)kd;
+  double r = fmad(-kd, kLn2Hi, xd);
+  r = fmad(-kd, kLn2Lo, r);
+  double p = 0x1.288088c0e67a5p-22;
+  p = fmad(p, r, 0x1.72c79824255e0p-19);
+  p = fmad(p, r, 0x1.a019c971b4d98p-16);
+  p = fmad(p, r, 0x1.a019ad55d1aa7p-13);
+  p = fmad(p, r, 0x1.6c16c1739a511p-10);
+  p = fmad(p, r, 0x1.1111111c5719ap-7);
+  p = fmad(p, r, 0x1.5555555554ca7p-5);
+  p = fmad(p, r, 0x1.5555555553b48p-3);
+  p = fmad(p, r, 0x1.0000000000000p-1);
+  const double q = fmad(r * r, p, r);
+  if (k == 0) return (float)q;
+  const double two_k = __longlong_as_double((long long)(k + 1023) << 52);  // 2^k, -151 <= k <= 128
+  return (float)fmad(two_k, q, two_k - 1.0);
+}
 
 // utils/math.py:156-172
 AGX_DEV Q4 quat_from_euler(float roll, float pitch, float yaw) {

@@ -35,6 +35,8 @@ enum {
                         // (u[0], u[1]), (u[4], u[5]), (u[8], u[9]) of the slot's twelve; uniforms 2 and 3 of a block are not used
   RNG_E2E_OBS_NOISE = 10,  // counter word 1 = env step; 12 draws -> 12 normals    (agx_end_to_end_obs, agx_post_step_end_to_end)
   RNG_RADAR_NOISE = 11,  // counter word 1 = env step; block = pooled cell       (agx_radar_image_obs)
+  RNG_VAE_EPS = 12,     // counter word 1 = env step; 16 blocks -> 64 uniforms -> 32 Box-Muller pairs: normals (2 p, 2 p + 1) from
+                        // uniforms (2 p, 2 p + 1)                                (agx_vae_sample, agx_vae_noise)
   RNG_ASSETS = 16,      // + asset index (< 2^16 assets)
   RNG_SENSOR_MOUNT = 1 << 16,  // + sensor index; counter word 1 = episode; 6 draws  (agx_sensor_mount_reset)
   RNG_DISTURB = 1 << 20 // + sub-step; counter word 1 = env step

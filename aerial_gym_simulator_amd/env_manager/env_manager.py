@@ -281,11 +281,18 @@ class EnvManager(BaseManager):
         zeros): the last wave of such a kernel stores signal[parity] = step_counter + 1 once every row
         is visible device-wide (AgxEnvBuffers.step_signal); the exchange waits on it on the device."""
         self._require_device()
+        self._refuse_exchange_rows()
         B = self._buffers
         B.step_rows[0], B.step_rows[1] = _lib.dptr(rows[0]), _lib.dptr(rows[1])
         B.step_reward = _lib.dptr(reward)
         B.step_signal = _lib.dptr(signal) if signal is not None else None
         self._step_rows = (rows, reward, signal)  # keep alive
+
+    exchange_rows_refusal = None  # a task whose observation is not completed by the row-writing kernels says why here
+
+    def _refuse_exchange_rows(self):
+        if self.exchange_rows_refusal:
+            raise RuntimeError(self.exchange_rows_refusal)
 
     # ---- peer push of the exchange rows by the observation kernels themselves (sharding.StepGather, backend "peer_push") ----
     _push = None
@@ -296,6 +303,7 @@ class EnvManager(BaseManager):
         kernels into slot (seq - 1) % slots of EVERY rank's buffer (AgxEnvBuffers.push_*): no launch and no host call per
         step for the exchange; `_begin_step()` moves the sequence number once per env step."""
         self._require_device()
+        self._refuse_exchange_rows()
         if world > 8:
             raise ValueError("peer push from the kernels covers one node (at most 8 ranks)")
         B = self._buffers

@@ -21,6 +21,8 @@ logger = CustomLogger("lidar_navigation_task")
 
 
 class LiDARNavigationTask(NavigationTask):
+    _vae_supported = False
+
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
         super().__init__(task_config, seed=seed, num_envs=num_envs, headless=headless, device=device, use_warp=use_warp)
         cfg, N, dev = self.task_config, self.num_envs, self.device

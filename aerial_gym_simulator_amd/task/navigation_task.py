@@ -3,9 +3,11 @@
 observation packing and the image min run in the HIP library; success / timeout bookkeeping
 and the curriculum stay as (tiny) host logic like the reference.
 
-The reference encodes the depth image with a pre-trained VAE (dense conv net, outside the
-simulation hot path); with `vae_config.use_vae = False` (default here) the 64
-latent slots carry an 8 x 8 min-pooled depth grid instead."""
+The reference encodes the depth image with a pre-trained VAE.  `vae_config.use_vae = True` does the
+same here: utils/vae/vae_image_encoder.py on the HIP kernels of csrc/agx_vae.hip
+fills `image_latents` in process_image_observation, and the 64 latent slots of the observation
+carry it.  With `vae_config.use_vae = False` (default here; the weight file is not shipped) the
+slots carry an 8 x 8 min-pooled depth grid instead."""
 import ctypes as C
 
 import numpy as np
@@ -44,9 +46,10 @@ class NavigationTask(BaseTask):
         self.pos_err_soa, self.prev_pos_err_soa = soa(3, N, dev), soa(3, N, dev)
         self.pos_error_vehicle_frame = aos_view(self.pos_err_soa)
         self.pos_error_vehicle_frame_prev = aos_view(self.prev_pos_err_soa)
-        if cfg.vae_config.use_vae:
-            raise NotImplementedError("the VAE image encoder is out of scope (SURVEY.md row 14); set use_vae = False")
         self.obs_dict = self.sim_env.get_obs()
+        self.vae_model = None
+        if cfg.vae_config.use_vae:
+            self._setup_vae()
         if "curriculum_level" not in self.obs_dict:
             self.curriculum_level = cfg.curriculum.min_level
             self.obs_dict["curriculum_level"] = self.curriculum_level
@@ -85,6 +88,38 @@ class NavigationTask(BaseTask):
         self._min_ratio = (C.c_float * 3)(*[float(v) for v in cfg.target_min_ratio])
         self._max_ratio = (C.c_float * 3)(*[float(v) for v in cfg.target_max_ratio])
         self._fuse_with_env()
+
+    _vae_supported = True  # (the LiDAR and radar tasks pool their range image themselves: they keep use_vae = False)
+
+    def _setup_vae(self):
+        """vae_config.use_vae: the reference's VAEImageEncoder (navigation_task.py:66-72) and `image_latents`.  Combinations that
+        would step with wrong latents are refused here."""
+        cfg, env = self.task_config, self.sim_env
+        vc = cfg.vae_config
+        if not self._vae_supported:
+            raise NotImplementedError(f"{type(self).__name__} builds its latents from the pooled range image: set vae_config.use_vae = False")
+        if env._buffers is None:
+            raise RuntimeError("vae_config.use_vae needs the HIP device buffers of the env")
+        if bool(self._arg("step_graph", False)):
+            raise ValueError("vae_config.use_vae with args['step_graph']: the encoder's env-step counter is a launch argument, a "
+                             "replayed graph would freeze it (and the chunk loop with it); step eagerly")
+        px = self.obs_dict.get("depth_range_pixels")
+        if px is None or px.dim() != 4 or px.shape[1] != 1:
+            raise ValueError("vae_config.use_vae encodes the depth image of ONE camera (the reference squeezes the sensor axis); "
+                             f"the robot has {'no camera' if px is None else tuple(px.shape)}")
+        if int(cfg.observation_space_dim) != 17 + int(vc.latent_dims):
+            raise ValueError(f"vae_config.use_vae: observation_space_dim = {cfg.observation_space_dim}, the observation is 17 + "
+                             f"latent_dims = {17 + int(vc.latent_dims)} wide")
+        from ..utils.vae.vae_image_encoder import VAEImageEncoder
+
+        self.vae_model = VAEImageEncoder(vc, device=self.device, workspace_mb=self._arg("vae_workspace_mb", VAEImageEncoder.DEFAULT_WORKSPACE_MB),
+                                         rng_seed=env.rng_seed)
+        self.vae_model.env_index_base = int(env.env_offset)
+        self.image_latents = torch.zeros((env.num_envs, int(vc.latent_dims)), device=self.device)
+        self._vae_eps = torch.zeros_like(self.image_latents)
+        # sharded stepping: the exchange rows are written by agx_obs_navigation, which no longer sees the latents
+        env.exchange_rows_refusal = ("vae_config.use_vae: the exchange rows of sharded stepping are written by the observation kernel "
+                                     "and would miss the VAE latents")
 
     def _arg(self, key, default):
         """switches of this task come through task_config.args as it was at construction (the dict that also reaches the
@@ -392,13 +427,31 @@ class NavigationTask(BaseTask):
         return ret
 
     def process_image_observation(self):
-        pass  # the min-pooled latents are written by agx_obs_navigation
+        """navigation_task.py:272-278: the frame just rendered -> image_latents.  Without the encoder the min-pooled latents
+        are written by agx_obs_navigation and there is nothing to do here.  strict_rng: the reparametrisation's normals are one
+        [N, 64] draw of the random source, taken whether or not the sampled latent is what is returned (the reference's
+        encode always draws); otherwise the library's generator at (rng_seed, global env index, env step)."""
+        enc = self.vae_model
+        if enc is None:
+            return
+        env = self.sim_env
+        if torch.cuda.is_current_stream_capturing():
+            # a caller capturing task.step() into a graph of their own: the env step is a launch argument of the encoder (every
+            # replay would draw the same eps) and its result tensors are allocated per call
+            raise RuntimeError("vae_config.use_vae: task.step() cannot be captured into a hipGraph (the encoder's env-step counter is "
+                               "a launch argument); step eagerly")
+        eps = None
+        if env.strict_rng:
+            eps = self.obs_dict["random_source"].normal_into(self._vae_eps, tag="vae_eps")
+        enc.env_step = int(env._buffers.step_counter)
+        z_sampled, means, _std = enc.encode_all(self.obs_dict["depth_range_pixels"], eps=eps)
+        self.image_latents.copy_(z_sampled if self.task_config.vae_config.return_sampled_latent else means)
 
     _min_pixel_in_obs = False
 
     def _image_min_fusable(self):
         px = self.obs_dict.get("depth_range_pixels")
-        return (px is not None and px.dim() == 4 and px.shape[1] == 1 and self.task_config.observation_space_dim > 17
+        return (self.vae_model is None and px is not None and px.dim() == 4 and px.shape[1] == 1 and self.task_config.observation_space_dim > 17
                 and not self.task_config.return_state_before_reset)
 
     def post_image_reward_addition(self):
@@ -438,7 +491,8 @@ class NavigationTask(BaseTask):
             rs = self.obs_dict["random_source"]
             uv, ue = _lib.dptr(rs.rand_into(self._u_vec, tag="obs_vec")), _lib.dptr(rs.rand_into(self._u_euler, tag="obs_euler"))
         px = self.obs_dict.get("depth_range_pixels")
-        use_px = px is not None and px.dim() == 4 and self.task_config.observation_space_dim > 17
+        # with the encoder the kernel leaves the latent slots alone (pixels = NULL) and image_latents is placed behind it
+        use_px = px is not None and px.dim() == 4 and self.task_config.observation_space_dim > 17 and self.vae_model is None
         S, H, W = (px.shape[1], px.shape[2], px.shape[3]) if use_px else (0, 0, 0)
         _lib.check(
             env._lib.agx_obs_navigation(env._buffers, env.num_envs, _lib.dptr(self.target_soa), uv, ue,
@@ -449,3 +503,8 @@ class NavigationTask(BaseTask):
                                         env._stream()),
             "agx_obs_navigation",
         )
+        if self.vae_model is not None:
+            if env._buffers.step_rows[0] or env._buffers.step_rows[1]:
+                raise RuntimeError(env.exchange_rows_refusal)
+            _lib.check(env._lib.agx_vae_place_latents(env.num_envs, _lib.dptr(self.image_latents), _lib.dptr(self.task_obs["observations"]),
+                                                      int(self.task_config.observation_space_dim), 17, env._stream()), "agx_vae_place_latents")

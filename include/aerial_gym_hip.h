@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 21
+#define AGX_ABI_VERSION 22
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -324,7 +324,8 @@ int agx_update_states(const AgxEnvBuffers *buf, int num_envs, void *stream);
  * base_lee_controller.py:136-215, the reward functions' torch.exp), on device vectors: out[i] = f(x[i]) (atan2:
  * atan2(x[i], y[i]), x = the "y" argument).  float64 inside, rounded once: correctly rounded in practice.  Diagnostic
  * entry: the parity tests compare it bit for bit with the CPU restatement.                                          */
-enum { AGX_MATH_SIN = 0, AGX_MATH_COS = 1, AGX_MATH_ATAN2 = 2, AGX_MATH_ASIN = 3, AGX_MATH_EXP = 4 };
+enum { AGX_MATH_SIN = 0, AGX_MATH_COS = 1, AGX_MATH_ATAN2 = 2, AGX_MATH_ASIN = 3, AGX_MATH_EXP = 4,
+       AGX_MATH_EXPM1 = 5 /* expm1_cw: the negative branch of ELU (agx_vae.hip), where torch evaluates expm1 */ };
 int agx_math_eval(int which, int n, const float *x, const float *y, float *out, void *stream);
 
 /* Diagnostic: float4 streaming copy of `bytes` (multiple of 16) from src to dst -- the HBM rate a kernel of this library
@@ -397,9 +398,10 @@ int agx_reward_navigation(const AgxEnvBuffers *buf, int num_envs, const float *t
  * row-major = unit vector to target (+0.2 U01 noise) | distance | roll, pitch (+-0.05 noise) | 0 |
  * body lin/ang velocity | robot_actions(4) | latents.  u_vec, u_euler: [N][3] U01 draws, or both
  * NULL = device generator (stream of (env, buf->step_counter)).
- * The reference fills the latents with a VAE encoding of the depth image (a conv net outside
- * the simulation hot path); here latents = grid_h x grid_w min-pooled depth image
- * (pixels [N][S][H][W], sensor 0), or left untouched when pixels == NULL.
+ * The reference fills the latents with a VAE encoding of the depth image: with vae_config.use_vae the
+ * host passes pixels == NULL, which leaves the latent slots untouched, and places the encoder's output
+ * there itself (the "VAE depth-image encoder" section at the end of this header).  Without the encoder
+ * latents = grid_h x grid_w min-pooled depth image (pixels [N][S][H][W], sensor 0).
  * min_pixel [N] (optional, num_sensors == 1 only): what agx_image_min would write
  * (post_image_reward_addition, navigation_task.py:351-357), produced by the same sweep over the
  * image.                                                                                    */
@@ -1078,6 +1080,73 @@ int agx_exchange_check(AgxExchange *x);
  * mapped addresses -- the way the observation kernels store rows --, raises a flag, waits at most timeout_ms for every rank's
  * flag and compares what arrived.  *passed = 1: this rank received every rank's word.  The buffers are left as found. */
 int agx_exchange_push_selftest(AgxExchange *x, int timeout_ms, int *passed, void *stream);
+
+/* ---- VAE depth-image encoder (aerial_gym/utils/vae/VAE.py ImgEncoder + the sampling of VAE.encode,
+ * vae_image_encoder.py:35-55) -----------------------------------------------------------------------------------------
+ * Nine convolutions, two dense layers and the reparametrisation, all fp32 on the exact-fp32 matrix instruction
+ * (v_mfma_f32_32x32x2_f32): every output element is ONE k-ordered fmaf chain over k = (ci, kh, kw) ascending from 0, then
+ * + bias, then (optionally) + a second tensor, then (optionally) ELU with alpha 1 -- each a rounded fp32 operation.  The
+ * order does not depend on batch size, env index, tile position or chunking.  DESIGN.md "VAE encoder".
+ *
+ * Weights reach the kernels repacked [K8][Cout] (k-major, K8 = K rounded up to a multiple of 8, the tail zero), K = Cin kh kw
+ * in torch's [Cout][Cin][kh][kw] order.  Pack and unpack are host functions on host memory.                              */
+enum { AGX_VAE_ELU = 1 };            /* flags of the single-layer entry points */
+enum { AGX_VAE_LAYERS = 11 };        /* conv0, conv0_1, conv1_0, conv1_1, conv0_jump_2, conv2_0, conv2_1, conv1_jump_3, conv3_0,
+                                        dense0, dense1: the order of every per-layer array below */
+typedef struct AgxVaeConv {
+  int32_t cin, cout;                 /* cout: a multiple of 32 */
+  int32_t kh, kw, stride;
+  int32_t pad_h, pad_w;
+  int32_t in_h, in_w;                /* the (zero-padded) input the taps index: the index tables' lengths when they are given */
+  int32_t out_h, out_w;              /* (in + 2 pad - k) / stride + 1 */
+  int32_t src_h, src_w;              /* rows and columns of x in memory: in_h, in_w unless index tables are given */
+} AgxVaeConv;
+size_t agx_vae_packed_floats(int cout, int k);
+int agx_vae_pack_weight(int cout, int k, const float *w /*[cout][k]*/, float *packed);
+int agx_vae_unpack_weight(int cout, int k, const float *packed, float *w);
+/* y [B][cout][out_h][out_w] <- conv(x [B][cin][src_h][src_w]) + bias [cout] (+ add, shaped like y) (ELU).  row_map [in_h],
+ * col_map [in_w] (int32, device; both or neither): the input is x gathered as x[b][ci][row_map[r]][col_map[c]] -- a
+ * nearest-neighbour resize that costs no pass of its own.  Everything is a DEVICE pointer but `shape`.                   */
+int agx_vae_conv2d(int batch, const float *x, const float *w_packed, const float *bias, const float *add, float *y,
+                   const AgxVaeConv *shape, int flags, const int32_t *row_map, const int32_t *col_map, void *stream);
+/* y [B][out_features] <- x [B][in_features] W^T + bias (ELU): the convolution kernel at 1 x 1 spatial size.              */
+int agx_vae_linear(int batch, const float *x, const float *w_packed, const float *bias, float *y, int in_features,
+                   int out_features, int flags, void *stream);
+/* out_hw [AGX_VAE_LAYERS][2]: output height and width of every layer for an image_h x image_w input (dense: 1 x 1).
+ * AGX_E_ARG unless the last convolution ends in 3 x 6 (x 128 = the 2304 inputs of dense0).  Host only.                    */
+int agx_vae_geometry(int image_h, int image_w, int32_t *out_hw);
+/* The reparametrisation (VAE.py:236-244) of z [N][128]: mean = z[:64], std = exp(0.5f * z[64:]) (exp_cw), latents = mean +
+ * eps * std -- each operation rounded.  eps [N][64], or NULL = the device generator: 64 standard normals per env, a function
+ * of (rng_seed, env_index_base + env, env_step) alone.  means, std: optional.                                             */
+int agx_vae_sample(int num_envs, const float *z, const float *eps, float *latents, float *means, float *std,
+                   uint64_t rng_seed, int env_index_base, int env_step, void *stream);
+/* Diagnostic: noise_out [N][64] <- the normals the NULL-eps form draws.                                                   */
+int agx_vae_noise(int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out, void *stream);
+/* obs [N][obs_dim], columns obs_offset .. obs_offset + 63 <- latents [N][64]                                              */
+int agx_vae_place_latents(int num_envs, const float *latents, float *obs, int obs_dim, int obs_offset, void *stream);
+
+/* The whole encoder.  Create: weights / biases = AGX_VAE_LAYERS HOST pointers each, torch's layouts ([Cout][Cin][kh][kw],
+ * [out][in]); the handle owns the repacked device copies (the only entry points of this section that allocate and
+ * synchronise).  AGX_E_ARG: latent_dims != 64, or an image_res agx_vae_geometry refuses.
+ * agx_vae_encode: pixels [N][src_h][src_w] -> latents / means / std [N][64] (means, std optional), in chunks of as many envs
+ * as `workspace` holds (agx_vae_workspace_bytes(handle, 1) at least); no allocation, no host synchronisation, no host
+ * randomness.  row_map / col_map as agx_vae_conv2d (NULL: src_h x src_w must be image_res).  It issues exactly the
+ * single-layer calls above, so its result equals theirs bit for bit, whatever the chunking.                               */
+typedef struct AgxVaeEncoder AgxVaeEncoder;
+int agx_vae_create(const float *const *weights, const float *const *biases, int image_h, int image_w, int latent_dims,
+                   AgxVaeEncoder **out);
+int agx_vae_destroy(AgxVaeEncoder *enc);
+size_t agx_vae_workspace_bytes(const AgxVaeEncoder *enc, int envs_per_chunk);
+/* The chunk size agx_vae_encode derives: as many envs as workspace_bytes holds, at most num_envs (0: not even one).  The
+ * workspace size is linear in the chunk, so agx_vae_workspace_bytes of n gives back exactly n.                              */
+int agx_vae_envs_per_chunk(const AgxVaeEncoder *enc, size_t workspace_bytes, int num_envs);
+int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pixels, int src_h, int src_w, const int32_t *row_map,
+                   const int32_t *col_map, const float *eps, float *latents, float *means, float *std, void *workspace,
+                   size_t workspace_bytes, uint64_t rng_seed, int env_index_base, int env_step, void *stream);
+/* Diagnostic: the device copies of layer `layer` (packed weights, bias) and the buffer of its output inside a workspace
+ * laid out for `envs_per_chunk` envs (byte offset).                                                                       */
+int agx_vae_layer_info(const AgxVaeEncoder *enc, int layer, int envs_per_chunk, const float **w_packed, const float **bias,
+                       size_t *out_offset_bytes);
 
 #ifdef __cplusplus
 }
