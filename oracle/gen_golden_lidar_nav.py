@@ -11,8 +11,17 @@ produced by running the REFERENCE's own code (build container only: needs /root/
   lidar_image_obs.npz          LiDARNavigationTask.process_image_observation (:313-363) and
                                add_noise_to_downsampled_lidar_data (:281-310), called as unbound methods on a
                                stand-in object; the random tensors the noise function draws are re-drawn
-                               from the same seed and stored next to the outputs
+                               from the same seed and stored next to the outputs.  With --cr (a bit-for-bit pin) also
+                               `overlap_*`: the same with the first seed whose draws put every pair of the three rules into
+                               one cell and a low value into the pooled rows 10 and 15
   obs_lidar_navigation.npz     LiDARNavigationTask.process_obs_for_task (:440-470), same technique
+  reward_frames_lidar_navigation.npz   (with --cr only: it is a bit-for-bit pin) LiDARNavigationTask.compute_rewards_and_crashes
+                               (:472-553), same technique, on general robot positions, vehicle-frame quaternions,
+                               robot_euler_angles and targets -> pos_error_vehicle_frame, the yaw error it hands to
+                               compute_reward, and the reward.  Rows 0-5 hold a yaw of exactly +-pi and its two float32
+                               neighbours; the number of rows in every class the kernel branches on is asserted below
+
+`--out DIR` writes everywhere else than into tests/golden/ (tests/golden/cr/ with --cr).
 """
 import json
 import math
@@ -31,7 +40,7 @@ import torch
 import oracle as orc
 import ref_shells
 
-OUT = gg.OUT
+OUT = _sys.argv[_sys.argv.index("--out") + 1] if "--out" in _sys.argv else gg.OUT
 
 
 def magpie_constants(cfg):
@@ -176,8 +185,8 @@ def gen_image_obs(rng, lt):
     pc = (pos[:, None, None, :] + dirs * rng_img[..., None]).unsqueeze(1).contiguous()
     linvel = torch.randn(n, 3, generator=rng) * 2
     linvel[0] = 0.0
-    out = {}
-    for tag, seed in (("clean", None), ("noisy", 77)):
+    def run(seed):
+        """process_image_observation on the cloud: without the noise function, or with it from torch.manual_seed(seed)"""
         fake = types.SimpleNamespace(
             obs_dict={"depth_range_pixels": pc.clone(), "robot_position": pos.clone(), "robot_linvel": linvel.clone()},
             world_dir_vectors=torch.ones(n, H, W, 3), num_envs=n, time_to_collision=torch.zeros(n),
@@ -188,22 +197,39 @@ def gen_image_obs(rng, lt):
             fake.add_noise_to_downsampled_lidar_data = types.MethodType(lt.LiDARNavigationTask.add_noise_to_downsampled_lidar_data, fake)
             torch.manual_seed(seed)
         lt.LiDARNavigationTask.process_image_observation(fake)
-        out[tag + "_ttc"] = fake.time_to_collision.numpy().copy()
-        out[tag + "_ds"] = fake.downsampled_lidar_data.numpy().copy()
-        if seed is not None:
-            # re-draw what add_noise_to_downsampled_lidar_data drew (:281-310), same seed, same call order
-            torch.manual_seed(seed)
-            z = torch.zeros(n, 16, 20)
-            noise_mask = torch.bernoulli(0.03 * torch.ones_like(z))
-            k1 = int((noise_mask == 1).sum())
-            noise_val_flat = m.torch_rand_float_tensor(0.2 * torch.ones(k1), 10.0 * torch.ones(k1))
-            noise_val = torch.zeros_like(z)
-            noise_val[noise_mask == 1] = noise_val_flat
-            max_mask = torch.bernoulli(0.02 * torch.ones_like(z))
-            low_mask = torch.bernoulli(0.02 * torch.ones_like(z[:, 10:]))
-            low_val = m.torch_rand_float_tensor(0.2 * torch.ones_like(low_mask), 1.0 * torch.ones_like(low_mask))
-            out.update(noise_mask=noise_mask.numpy(), noise_val=noise_val.numpy(), max_mask=max_mask.numpy(),
-                       low_mask=low_mask.numpy(), low_val=low_val.numpy())
+        return fake.time_to_collision.numpy().copy(), fake.downsampled_lidar_data.numpy().copy()
+
+    def draws(seed):
+        """what add_noise_to_downsampled_lidar_data draws (:286-310), same seed, same call order"""
+        torch.manual_seed(seed)
+        z = torch.zeros(n, 16, 20)
+        noise_mask = torch.bernoulli(0.03 * torch.ones_like(z))
+        k1 = int((noise_mask == 1).sum())
+        noise_val_flat = m.torch_rand_float_tensor(0.2 * torch.ones(k1), 10.0 * torch.ones(k1))
+        noise_val = torch.zeros_like(z)
+        noise_val[noise_mask == 1] = noise_val_flat
+        max_mask = torch.bernoulli(0.02 * torch.ones_like(z))
+        low_mask = torch.bernoulli(0.02 * torch.ones_like(z[:, 10:]))
+        low_val = m.torch_rand_float_tensor(0.2 * torch.ones_like(low_mask), 1.0 * torch.ones_like(low_mask))
+        return dict(noise_mask=noise_mask.numpy(), noise_val=noise_val.numpy(), max_mask=max_mask.numpy(), low_mask=low_mask.numpy(),
+                    low_val=low_val.numpy())
+
+    def rules_meet(d):
+        """two rules in one cell, every pair, and a low value in the first and in the last pooled row that can hold one"""
+        nm, mm = d["noise_mask"] == 1, d["max_mask"] == 1
+        lm = np.concatenate([np.zeros((n, 10, 20), bool), d["low_mask"] == 1], axis=1)
+        return bool((nm & mm & ~lm).any() and (mm & lm).any() and (nm & lm & ~mm).any() and lm[:, 10].any() and lm[:, 15].any())
+
+    out = {}
+    out["clean_ttc"], out["clean_ds"] = run(None)
+    out["noisy_ttc"], out["noisy_ds"] = run(77)
+    out.update(draws(77))
+    if gg.CR:
+        # (bit-for-bit pin only) the first seed whose draws make the rules meet: the order noise, max, low and the first low row show
+        seed = next(sd for sd in range(1000, 4000) if rules_meet(draws(sd)))
+        out["overlap_ttc"], out["overlap_ds"] = run(seed)
+        out.update({"overlap_" + k: v for k, v in draws(seed).items()}, overlap_seed=np.int64(seed))
+        print("lidar_image_obs: the rules meet with seed", seed)
     np.savez(os.path.join(OUT, "lidar_image_obs.npz"), pointcloud=pc.numpy(), robot_position=pos.numpy(), robot_linvel=linvel.numpy(), **out)
     print("lidar_image_obs: ok  ttc", out["clean_ttc"], " noisy != clean:", int((out["noisy_ds"] != out["clean_ds"]).sum()))
 
@@ -234,7 +260,79 @@ def gen_obs(rng, lt):
     print("obs_lidar_navigation: ok")
 
 
+def gen_reward_frames(lt, cfg):
+    n = 768
+    rng = torch.Generator().manual_seed(772)  # its own generator: the fixtures above keep their draws
+    m = ref_shells.ref("utils.math")
+    f32, pi = np.float32, np.float32(np.pi)
+    quat = gg.random_state(n, rng, spread=5.0)[:, 3:7]
+    qveh = m.vehicle_frame_quat_from_quat(quat)
+    euler = m.get_euler_xyz_tensor(quat)          # [0, 2 pi): both sides of +pi
+    euler[1::2] -= 2.0 * math.pi                  # [-2 pi, 0): both sides of -pi
+    edge = [pi, np.nextafter(pi, f32(0)), np.nextafter(pi, f32(4)), -pi, np.nextafter(-pi, f32(0)), np.nextafter(-pi, f32(-4))]
+    euler[0:6, 2] = torch.tensor(np.array(edge, np.float32))
+    pos = torch.randn(n, 3, generator=rng) * 5
+    offset = torch.randn(n, 3, generator=rng) * 3
+    offset[: n // 6] *= 0.15                      # inside the 1 m "stable at goal" radius
+    target = pos + offset
+    tyaw = (torch.rand(n, generator=rng) - 0.5) * 2 * math.pi
+    vveh = torch.randn(n, 3, generator=rng) * 1.5
+    vveh[::7] *= 3.0
+    vveh[5::64] = 0.0                             # at rest: the -0.2 branch of the velocity-direction term
+    wbody = torch.randn(n, 3, generator=rng)
+    crashes = torch.rand(n, generator=rng) < 0.1
+    act = (torch.rand(n, 4, generator=rng) - 0.5) * 4
+    pact = (torch.rand(n, 4, generator=rng) - 0.5) * 4
+    ttc = torch.rand(n, generator=rng) * 3
+    ttc[::5] = 10.0
+    cpf = 0.35
+    prev = torch.randn(n, 3, generator=rng)
+    fake = types.SimpleNamespace(
+        target_position=target.clone(), target_yaw=tyaw.clone(), device="cpu", pos_error_vehicle_frame=prev.clone(),
+        pos_error_vehicle_frame_prev=torch.zeros(n, 3), current_action=act.clone(), prev_action=pact.clone(),
+        time_to_collision=ttc.clone(), curriculum_progress_fraction=cpf,
+        task_config=types.SimpleNamespace(reward_parameters={k: torch.tensor(float(cfg.reward_parameters[k])) for k in REWARD_KEYS}))
+    fake.obs_dict = {"robot_position": pos.clone(), "robot_vehicle_orientation": qveh.clone(), "robot_orientation": quat.clone(),
+                     "robot_euler_angles": euler.clone(), "robot_vehicle_linvel": vveh.clone(), "robot_body_angvel": wbody.clone(),
+                     "crashes": crashes.clone()}
+    seen = {}
+    real = lt.compute_reward
+
+    def recording(*args):  # the yaw error is a local of compute_rewards_and_crashes: taken where it is handed on
+        seen["yaw_error"] = args[4].clone()
+        return real(*args)
+
+    lt.compute_reward = recording
+    try:
+        r, c = lt.LiDARNavigationTask.compute_rewards_and_crashes(fake, fake.obs_dict)
+    finally:
+        lt.compute_reward = real
+    pe, ye = fake.pos_error_vehicle_frame, seen["yaw_error"]
+    assert torch.equal(fake.pos_error_vehicle_frame_prev, prev) and torch.equal(c, crashes)
+    yaw, dist, speed = euler[:, 2], pe.norm(dim=1), vveh.norm(dim=1)
+    wrapped = tyaw - m.ssa(yaw)
+    classes = {
+        "yaw just below +pi": int(((yaw > math.pi - 0.5) & (yaw < math.pi)).sum()), "yaw just above +pi": int(((yaw > math.pi) & (yaw < math.pi + 0.5)).sum()),
+        "yaw just above -pi": int(((yaw < -math.pi + 0.5) & (yaw > -math.pi)).sum()), "yaw just below -pi": int(((yaw < -math.pi) & (yaw > -math.pi - 0.5)).sum()),
+        "target_yaw - yaw above +pi": int((wrapped > math.pi).sum()), "target_yaw - yaw below -pi": int((wrapped < -math.pi).sum()),
+        "target_yaw - yaw within +-pi": int((wrapped.abs() < math.pi).sum()),
+        "dist < 1": int((dist < 1).sum()), "1 < dist < 3": int(((dist > 1) & (dist < 3)).sum()), "dist > 3": int((dist > 3).sum()),
+        "at rest": int((speed == 0).sum()), "moving": int((speed > 0).sum()), "crashes": int(crashes.sum()),
+    }
+    floor = {"at rest": 10, "crashes": 30, "yaw just below +pi": 15, "yaw just above +pi": 15, "yaw just above -pi": 15, "yaw just below -pi": 15}
+    for name, count in classes.items():
+        assert count >= floor.get(name, 50), (name, count)
+    assert classes["at rest"] == 12 and (ye.abs() <= math.pi).all() and (r[crashes] == float(cfg.reward_parameters["collision_penalty"])).all()
+    np.savez(os.path.join(OUT, "reward_frames_lidar_navigation.npz"), robot_position=pos.numpy(), robot_vehicle_orientation=qveh.numpy(),
+             robot_euler_angles=euler.numpy(), target=target.numpy(), target_yaw=tyaw.numpy(), vveh=vveh.numpy(), wbody=wbody.numpy(),
+             crashes=crashes.numpy(), action=act.numpy(), prev_action=pact.numpy(), time_to_collision=ttc.numpy(),
+             curriculum_progress=np.float32(cpf), rp=np.array([float(cfg.reward_parameters[k]) for k in REWARD_KEYS], np.float32),
+             prev_pos_err=prev.numpy(), pos_err=pe.numpy(), yaw_error=ye.numpy(), reward=r.numpy())
+    print("reward_frames_lidar_navigation: ok ", classes)
+
+
 def main():
+    os.makedirs(OUT, exist_ok=True)
     rng = torch.Generator().manual_seed(4242)
     ref_shells.install()
     ref_shells.install_task_shells()
@@ -256,6 +354,8 @@ def main():
     gen_reward(rng, lt, cfg)
     gen_image_obs(rng, lt)
     gen_obs(rng, lt)
+    if gg.CR:
+        gen_reward_frames(lt, cfg)
 
 
 if __name__ == "__main__":

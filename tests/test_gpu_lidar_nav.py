@@ -1,11 +1,15 @@
-"""GPU parity of the LiDAR-navigation kernels through the C ABI: vs the CPU oracle and
-vs the golden vectors generated from the reference's own code, plus the task end to end."""
+"""GPU parity of the LiDAR-navigation kernels through the C ABI: bit for bit with the CPU oracle, within the bounds
+of tests/test_oracle_vs_reference.py of the golden vectors generated from the reference's own code as plain torch evaluates it, plus
+the task end to end against the restatements of tests/lidar_ref.py on the tensors its kernels read (the kernels at their limits:
+tests/test_gpu_lidar_nav_limits.py)."""
 import ctypes as C
 
+import lidar_ref as L
 import numpy as np
 import pytest
 import torch
 from conftest import golden_params, load_golden, rel_err
+from task_test_util import bits, host, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -49,9 +53,11 @@ def test_reward_lidar_navigation_vs_reference_and_oracle(orc):
     torch.cuda.synchronize()
     r = rew.cpu().numpy()
     assert rel_err(r, g["reward"]) < 1e-5  # vs the reference's own compute_reward
-    ref = orc.reward_lidar_navigation(g["pos_err"], g["vveh"], g["wbody"], g["yaw_error"], g["crashes"], g["action"], g["prev_action"],
+    # the oracle on what the kernel derives from the buffers: ssa(target_yaw - ssa(0)) may be one rounding away from target_yaw
+    pe_ref, ye_ref = L.reward_inputs(g["pos_err"], state[:, 0:3], derived[:, 3:7], derived[:, 2], g["yaw_error"])
+    ref = orc.reward_lidar_navigation(pe_ref, g["vveh"], g["wbody"], ye_ref, g["crashes"], g["action"], g["prev_action"],
                                       g["time_to_collision"], float(g["curriculum_progress"]), g["rp"])
-    assert rel_err(r, ref) < 1e-5
+    assert same_bits(pe_ref, g["pos_err"]) and same_bits(r, ref), np.abs(r - ref).max()
     assert np.array_equal(pe.cpu().numpy().T, g["pos_err"]) and np.all(ppe.cpu().numpy() == 7.0)  # prev <- cur, cur <- new
     trunc = (np.arange(n) % 130) > 110
     assert np.array_equal(H.trunc.cpu().numpy(), trunc)  # flags: bit-exact
@@ -81,7 +87,7 @@ def test_lidar_image_obs_bit_exact(orc):
 
     got_ttc, got_ds = run([None] * 5)
     ref_ttc, ref_ds = orc.lidar_image_obs(pc, g["robot_position"], g["robot_linvel"])
-    assert np.array_equal(got_ttc, ref_ttc) and np.array_equal(got_ds, ref_ds)     # vs oracle: bit-exact
+    assert same_bits(got_ttc, ref_ttc) and same_bits(got_ds, ref_ds)     # vs oracle: bit-exact
     assert rel_err(got_ttc, g["clean_ttc"]) < 2e-6 and rel_err(got_ds, g["clean_ds"]) < 2e-6  # vs reference
     # the kernel reads a 16-byte-aligned cloud with 16-byte loads (four points per three loads); a cloud that starts 4 bytes off
     # takes the 4-byte path: same bits
@@ -99,6 +105,8 @@ def test_lidar_image_obs_bit_exact(orc):
     noise_t = [T(a) for a in noise_np]
     got_ttc2, got_ds2 = run(noise_t)
     assert rel_err(got_ds2, g["noisy_ds"]) < 2e-6 and np.array_equal(got_ttc2, got_ttc)
+    ref_ttc2, ref_ds2 = orc.lidar_image_obs(pc, g["robot_position"], g["robot_linvel"], **dict(zip(("noise_mask", "noise_val", "max_mask", "low_mask", "low_val"), noise_np)))
+    assert same_bits(got_ds2, ref_ds2) and same_bits(got_ttc2, ref_ttc2)  # vs oracle: bit-exact
     # device generator: Philox stream RNG_LIDAR_NOISE of (env, step), blocks 2c / 2c+1 of pooled cell c
     H.B.rng_seed, H.B.step_counter = 1234567, 41
     got_ttc3, got_ds3 = run([None] * 5, device_noise=1)
@@ -111,7 +119,7 @@ def test_lidar_image_obs_bit_exact(orc):
     lv = ((f32(1.0) - f32(0.2)) * u[..., 4] + f32(0.2)).astype(f32)
     _, ref_ds3 = orc.lidar_image_obs(pc, g["robot_position"], g["robot_linvel"], noise_mask=nm, noise_val=nv, max_mask=mm,
                                      low_mask=lm, low_val=lv)
-    assert np.array_equal(got_ds3, ref_ds3) and np.array_equal(got_ttc3, got_ttc)
+    assert same_bits(got_ds3, ref_ds3) and same_bits(got_ttc3, got_ttc)
     changed = (got_ds3 != got_ds).mean()
     assert 0.03 < changed < 0.09  # ~3 % + 2 % + 2 % of 3/8 of the cells
 
@@ -132,11 +140,11 @@ def test_obs_lidar_navigation_vs_reference_and_oracle(orc):
     o = obs.cpu().numpy()
     ref = orc.obs_lidar_navigation(g["state"], g["euler"], g["qveh"], g["vbody"], g["wbody"], g["actions"], g["target"],
                                    g["target_yaw"], g["u_vec"], g["u_euler"], g["downsampled"])
+    assert same_bits(o, ref), np.argwhere(bits(o) != bits(ref))[:8]  # vs oracle: bit-exact, the yaw error of column 6 included
     keep = np.r_[0:6, 7:337]
-    for other, tol in ((ref, 1e-6), (g["obs"], 3e-6)):
-        d = np.abs(o[:, 6] - other[:, 6])
-        assert np.minimum(d, 2 * np.pi - d).max() < 3e-6
-        assert rel_err(o[:, keep], other[:, keep]) < tol
+    d = np.abs(o[:, 6] - g["obs"][:, 6])  # vs the reference as plain torch evaluates it: the yaw error wraps at +-pi
+    assert np.minimum(d, 2 * np.pi - d).max() < 3e-6
+    assert rel_err(o[:, keep], g["obs"][:, keep]) < 3e-6
     assert np.array_equal(o[:, 17:], g["downsampled"])
     # device generator for the two rand_like draws
     H.B.rng_seed, H.B.step_counter = 99, 7
@@ -145,60 +153,175 @@ def test_obs_lidar_navigation_vs_reference_and_oracle(orc):
     u6 = orc.rng_fill(99, np.full(n, 7), RNG_OBS_NOISE, 6)
     ref2 = orc.obs_lidar_navigation(g["state"], g["euler"], g["qveh"], g["vbody"], g["wbody"], g["actions"], g["target"],
                                     g["target_yaw"], u6[:, 0:3], u6[:, 3:6], g["downsampled"])
-    assert rel_err(obs.cpu().numpy()[:, keep], ref2[:, keep]) < 1e-6
+    assert same_bits(obs.cpu().numpy(), ref2)
 
 
 def test_magpie_substeps_vs_oracle_and_reference(orc):
-    """magpie + magpie_acceleration_control (root-link wrench mode, randomised gains): fused sub-steps."""
+    """magpie + magpie_acceleration_control (root-link wrench mode, randomised gains): fused sub-steps on the record's 64 rows and on
+    its leading 1 and 63 -- state and motor thrusts equal the oracle's bit for bit after 1 and after 10 sub-steps (the oracle's own
+    sub-step outputs equal the correctly rounded reference's bit for bit: tests/test_lidar_navigation_task.py)."""
+    for n in (64, 1, 63):
+        _magpie_substeps(orc, n)
+
+
+def _magpie_substeps(orc, n):
     from gpu_harness import DynHarness
 
     g = load_golden("step_magpie_acceleration")
     pd = golden_params(g)
-    n = g["state"].shape[1]
+    assert g["state"].shape[1] == 64
     P = orc.make_params(pd)
+    row = {k: np.ascontiguousarray(g[k][:n]) for k in ("kT", "tau_inc", "tau_dec", "Kp", "Kv", "KR", "Kw")}
+    state0, thrust0, action = (np.ascontiguousarray(g[k][0][:n]) for k in ("state", "thrust_in", "action"))
     H = DynHarness(pd, n)
-    H.set(kT=g["kT"], tau_inc=g["tau_inc"], tau_dec=g["tau_dec"], state=g["state"][0], thrust=g["thrust_in"][0])
-    H.set_gains(g["Kp"], g["Kv"], g["KR"], g["Kw"])
-    H.substeps(g["action"][0], 1)
-    assert rel_err(H.get("thrust"), g["thrust_out"][0]) < 1e-5   # the reference's own motor-model output
-    st, th = g["state"][0].copy(), g["thrust_in"][0].copy()
-    orc.substep(P, st, g["action"][0], th, g["kT"], g["tau_inc"], g["tau_dec"], g["Kp"], g["Kv"], g["KR"], g["Kw"],
-                disturb_max=g["disturb_max"])
-    assert rel_err(H.get("state"), st) < 1e-5
-    for _ in range(9):
-        orc.substep(P, st, g["action"][0], th, g["kT"], g["tau_inc"], g["tau_dec"], g["Kp"], g["Kv"], g["KR"], g["Kw"],
+    H.set(kT=row["kT"], tau_inc=row["tau_inc"], tau_dec=row["tau_dec"], state=state0, thrust=thrust0)
+    H.set_gains(row["Kp"], row["Kv"], row["KR"], row["Kw"])
+    H.substeps(action, 1)
+    assert rel_err(H.get("thrust"), g["thrust_out"][0][:n]) < 1e-5   # the reference's own motor-model output, as plain torch evaluates it
+    st, th = state0.copy(), thrust0.copy()
+
+    def oracle_substep():
+        orc.substep(P, st, action, th, row["kT"], row["tau_inc"], row["tau_dec"], row["Kp"], row["Kv"], row["KR"], row["Kw"],
                     disturb_max=g["disturb_max"])
-    H.substeps(g["action"][0], 9)
-    assert rel_err(H.get("state"), st) < 1e-4 and rel_err(H.get("thrust"), th) < 1e-4
+
+    oracle_substep()
+    got_state, got_thrust = H.get("state"), H.get("thrust")
+    print("magpie n = %d, 1 sub-step: max |state - oracle| %.3g, max |thrust - oracle| %.3g" % (n, np.abs(got_state - st).max(), np.abs(got_thrust - th).max()))
+    assert same_bits(got_state, st) and same_bits(got_thrust, th)
+    for _ in range(9):
+        oracle_substep()
+    H.substeps(action, 9)
+    got_state, got_thrust = H.get("state"), H.get("thrust")
+    print("magpie n = %d, 10 sub-steps: max |state - oracle| %.3g, max |thrust - oracle| %.3g" % (n, np.abs(got_state - st).max(), np.abs(got_thrust - th).max()))
+    assert same_bits(got_state, st) and same_bits(got_thrust, th)
+    assert np.abs(st - state0).max() > 1e-3  # ten sub-steps moved the state
 
 
-@pytest.mark.parametrize("strict", [False, True])
-def test_lidar_navigation_task_runs(strict):
-    """Reference names end to end: task_registry.make_task("lidar_navigation_task") = magpie +
-    magpie_acceleration_control + RS-LiDAR dome in env_with_lidar_nav_obstacles; 337-D observation."""
+def _make(n, strict, seed=3):
     import aerial_gym_simulator_amd  # noqa: F401
     from aerial_gym_simulator_amd.config.task_config import lidar_navigation_task_config as cfg
     from aerial_gym_simulator_amd.registry.task_registry import task_registry
 
+    old = {k: getattr(cfg, k) for k in ("seed", "num_envs", "headless", "device", "use_warp", "args")}
     cfg.device, cfg.args = DEV, {"strict_rng": strict}
     try:
-        n = 48
-        task = task_registry.make_task("lidar_navigation_task", seed=3, num_envs=n, headless=True)
-        obs, *_ = task.reset()
-        assert obs["observations"].shape == (n, 337) and task.task_config.robot_name == "magpie"
-        a = torch.rand(n, 4, device=DEV) * 2 - 1
-        resets = 0
-        for i in range(140):
-            obs, rew, term, trunc, info = task.step(a)
-            resets += int((term | trunc).sum())
-        o = obs["observations"]
-        assert torch.isfinite(o).all() and torch.isfinite(rew).all()
-        assert resets >= n  # episode_len 110: every env ended at least once
-        inv = o[:, 17:]
-        assert float(inv.min()) >= 1.0 / 20.0 - 1e-6 and float(inv.max()) <= 5.0 + 1e-5  # 1 / [0.2, 10 (+10 noise)]
-        assert float(task.time_to_collision.min()) >= 0.0 and float(task.time_to_collision.max()) <= 10.0
-        assert torch.equal(task.prev_action, task.action_transformation_function(a))  # the last two actions were identical
-        px = task.obs_dict["depth_range_pixels"]
-        assert px.shape == (n, 1, 48, 120, 3)
+        return task_registry.make_task("lidar_navigation_task", seed=seed, num_envs=n, headless=True)
     finally:
-        cfg.args = {}
+        for k, v in old.items():
+            setattr(cfg, k, v)
+
+
+@pytest.mark.parametrize("strict", [False, True])
+def test_lidar_navigation_task_runs(orc, strict):
+    """Reference names end to end: task_registry.make_task("lidar_navigation_task") = magpie + magpie_acceleration_control + RS-LiDAR
+    dome in env_with_lidar_nav_obstacles; 337-D observation; 48 envs, 140 steps of a fixed random action (episodes of 110 steps:
+    every env ends at least once).  The last step's pooled image, time to collision, reward and observation equal the restatements
+    (tests/lidar_ref.py) on the tensors the kernels read, bit for bit: in strict mode with the noise tensors the task drew, in the
+    default mode with the draws of the device generator re-made by the oracle from (seed, global env index, env-step index)."""
+    n, steps = 48, 140
+    task = _make(n, strict)
+    env, d = task.sim_env, task.obs_dict
+    snap, armed = {}, []  # (the hooks copy to the host in the last step only)
+    real_image, real_reward, real_obs = task.process_image_observation, task.compute_rewards_and_crashes, task.process_obs_for_task
+
+    def rng_key():
+        B = env._buffers
+        assert not B.step_counter_dev  # eager stepping: the env-step index is a launch argument
+        return dict(seed=int(B.rng_seed), step=int(B.step_counter), base=int(B.env_index_base))
+
+    def hooked_image():
+        if not armed:
+            return real_image()
+        snap["image"] = {k: host(d[k]).copy() for k in ("depth_range_pixels", "robot_position", "robot_linvel")}
+        snap["image"].update(rng_key())
+        return real_image()
+
+    def hooked_reward(obs_dict):
+        if not armed:
+            return real_reward(obs_dict)
+        snap["reward"] = {k: host(d[k]).copy() for k in ("robot_position", "robot_vehicle_orientation", "robot_euler_angles",
+                                                          "robot_vehicle_linvel", "robot_body_angvel", "crashes")}
+        snap["reward"].update(target=host(task.target_position).copy(), target_yaw=host(task.target_yaw).copy(),
+                              action=host(task.current_action).copy(), prev_action=host(task.prev_action).copy(),
+                              ttc=host(task.time_to_collision).copy(), cpf=float(task.curriculum_progress_fraction),
+                              pos_err=host(task.pos_error_vehicle_frame).copy())
+        return real_reward(obs_dict)
+
+    def hooked_obs():
+        if not armed:
+            return real_obs()
+        snap["obs"] = {k: host(d[k]).copy() for k in ("robot_position", "robot_vehicle_orientation", "robot_euler_angles", "robot_body_linvel",
+                                                       "robot_body_angvel", "robot_actions")}
+        snap["obs"].update(target=host(task.target_position).copy(), target_yaw=host(task.target_yaw).copy(),
+                           downsampled=host(task.downsampled_lidar_data).copy(), **rng_key())
+        r = real_obs()
+        if strict:  # the two rand_like draws of this call
+            snap["obs"].update(u_vec=host(task._u_vec).copy(), u_euler=host(task._u_euler).copy())
+        return r
+
+    task.process_image_observation, task.compute_rewards_and_crashes, task.process_obs_for_task = hooked_image, hooked_reward, hooked_obs
+    obs, *_ = task.reset()
+    assert obs["observations"].shape == (n, 337) and task.task_config.robot_name == "magpie" and env.robot_name == "magpie"
+    a = torch.rand(n, 4, device=DEV) * 2 - 1
+    resets = 0
+    for i in range(steps):
+        if i == steps - 1:
+            armed.append(True)
+        obs, rew, term, trunc, info = task.step(a)
+        resets += int((term | trunc).sum())
+    torch.cuda.synchronize()
+    o = obs["observations"]
+    assert torch.isfinite(o).all() and torch.isfinite(rew).all()
+    assert resets >= n  # episode_len 110: every env ended at least once
+    inv = o[:, 17:]
+    assert float(inv.min()) >= 1.0 / 20.0 - 1e-6 and float(inv.max()) <= 5.0 + 1e-5  # 1 / [0.2, 10 (+10 noise)]
+    assert float(task.time_to_collision.min()) >= 0.0 and float(task.time_to_collision.max()) <= 10.0
+    assert torch.equal(task.prev_action, task.action_transformation_function(a))  # the last two actions were identical
+    px = task.obs_dict["depth_range_pixels"]
+    assert px.shape == (n, 1, 48, 120, 3)
+    # the last step's image and time to collision
+    s = snap["image"]
+    oh, ow, cells, r0 = 16, 20, 320, int(task.task_config.lidar_low_noise_row0)
+    assert (task._H // task._ph, task._W // task._pw, r0) == (oh, ow, 10)
+    if strict:
+        masks = [host(t).reshape(n, cells) for t in task._noise]
+        assert set(np.unique(masks[0])) <= {0.0, 1.0} and not masks[3][:, : r0 * ow].any() and masks[0].any() and masks[2].any() and masks[3].any()
+    else:
+        assert task._noise is None
+        masks = [m[s["base"]:] for m in L.device_noise(orc, s["seed"], np.full(s["base"] + n, s["step"]), cells, ow, r0)]
+    ttc_ref, ds_ref = L.image_obs(orc, s["depth_range_pixels"][:, 0], s["robot_position"], s["robot_linvel"], *masks, low_row0=r0)
+    assert same_bits(host(task.time_to_collision), ttc_ref) and same_bits(host(task.downsampled_lidar_data), ds_ref)
+    clean = L.image_obs(orc, s["depth_range_pixels"][:, 0], s["robot_position"], s["robot_linvel"])[1]
+    print("lidar task, strict" if strict else "lidar task, default", "cells of the last image the noise changed: %d of %d" % ((clean != ds_ref).sum(), ds_ref.size))
+    assert 0.02 * ds_ref.size < (clean != ds_ref).sum() < 0.10 * ds_ref.size  # ~3 % + 2 % + 2 % of 3/8 of the cells
+    # ... its reward
+    s = snap["reward"]
+    pe, ye = L.reward_inputs(s["target"], s["robot_position"], s["robot_vehicle_orientation"], s["robot_euler_angles"][:, 2], s["target_yaw"])
+    cfg = task.task_config
+    rp = np.array([cfg.reward_parameters[k] for k in cfg.REWARD_PARAMETER_ORDER], np.float32)
+    want = L.lidar_reward(pe, s["robot_vehicle_linvel"], s["robot_body_angvel"], ye, s["crashes"], s["action"], s["prev_action"], s["ttc"], s["cpf"], rp)
+    assert same_bits(host(rew), want), np.abs(host(rew) - want).max()
+    assert same_bits(host(task.pos_error_vehicle_frame), pe) and same_bits(host(task.pos_error_vehicle_frame_prev), s["pos_err"])
+    assert (s["robot_vehicle_linvel"][:, 0] < 0).any() and (s["robot_vehicle_linvel"][:, 0] > 0).any()
+    assert (L.reward(pe, s["robot_vehicle_linvel"], s["robot_body_angvel"], ye, s["crashes"], s["action"], s["prev_action"], s["ttc"], s["cpf"], rp) != want).any()
+    # ... and its 337-D observation
+    s = snap["obs"]
+    uv, ue = (s["u_vec"], s["u_euler"]) if strict else (m[s["base"]:] for m in L.obs_draws(orc, s["seed"], np.full(s["base"] + n, s["step"])))
+    want = L.obs(s["robot_position"], s["robot_vehicle_orientation"], s["robot_euler_angles"], s["robot_body_linvel"], s["robot_body_angvel"],
+                 s["robot_actions"], s["target"], s["target_yaw"], uv, ue, s["downsampled"])
+    assert same_bits(s["downsampled"], ds_ref) and same_bits(host(o), want), np.argwhere(bits(host(o)) != bits(want))[:8]
+    task.close()
+
+
+def test_two_strict_lidar_tasks_of_one_seed_agree():
+    n = 48
+    runs = []
+    a = (torch.rand(n, 4, generator=torch.Generator().manual_seed(8)) * 2 - 1).to(DEV)
+    for _ in range(2):
+        task = _make(n, True, seed=11)
+        seq = [host(task.reset()[0]["observations"]).copy()]
+        for _ in range(5):
+            seq.append(host(task.step(a)[0]["observations"]).copy())
+        runs.append(np.stack(seq))
+        task.close()
+    assert same_bits(runs[0], runs[1]) and np.isfinite(runs[0]).all() and not np.array_equal(runs[0][0], runs[0][-1])

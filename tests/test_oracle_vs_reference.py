@@ -421,7 +421,10 @@ def test_cr_goldens_are_reproducible_and_torchscript_changes_no_bit(tmp_path):
     subprocess.run([sys.executable, "-c", code % cr_dir], check=True, capture_output=True, timeout=600,
                    env=dict(os.environ, AGX_GOLDEN_CR="1"))
     made = _compare_fixture_dirs(cr_dir, os.path.join(ROOT, "tests", "golden", "cr"))
-    assert len(made) == 26 and sorted(made) == sorted(os.listdir(os.path.join(ROOT, "tests", "golden", "cr")))
+    # the folder holds those 26 and the five fixtures of gen_golden_lidar_nav.py (tests/test_lidar_navigation_task.py regenerates them)
+    lidar_nav = [n + ".npz" for n in ("reward_lidar_navigation", "reward_frames_lidar_navigation", "lidar_image_obs", "obs_lidar_navigation",
+                                      "step_magpie_acceleration")]
+    assert len(made) == 26 and sorted(made + lidar_nav) == sorted(os.listdir(os.path.join(ROOT, "tests", "golden", "cr")))
     subprocess.run([sys.executable, "-c", code % jit_dir], check=True, capture_output=True, timeout=600,
                    env=dict(os.environ, AGX_GOLDEN_JIT="1"))
     n = 0
