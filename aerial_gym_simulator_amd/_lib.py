@@ -306,7 +306,20 @@ class AgxVaeConv(C.Structure):
 
 VAE_ELU, VAE_LAYERS, MATH_EXPM1 = 1, 11, 5  # AGX_VAE_ELU, AGX_VAE_LAYERS, AGX_MATH_EXPM1
 
-ABI_VERSION = 22  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+SNAPSHOT_MAX_ENTRIES = 96  # AGX_SNAPSHOT_MAX_ENTRIES
+SNAP_SOA, SNAP_AOS, SNAP_GLOBAL = 0, 1, 2  # AGX_SNAP_*
+
+
+class AgxSnapshotEntry(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("rows", C.c_int32), ("block_row", C.c_int32), ("elem_size", C.c_int32), ("layout", C.c_int32)]
+
+
+class AgxSnapshotTable(C.Structure):
+    """the live tensors a snapshot packs (agx_state_gather / agx_state_scatter; built by snapshot.StateTable)"""
+    _fields_ = [("count", C.c_int32), ("block_rows", C.c_int32), ("error", C.c_void_p), ("entry", AgxSnapshotEntry * SNAPSHOT_MAX_ENTRIES)]
+
+
+ABI_VERSION = 23  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -462,6 +475,9 @@ _SIGNATURES = {
     "agx_vae_envs_per_chunk": (C.c_int, [_P, C.c_size_t, C.c_int]),
     "agx_vae_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
     "agx_vae_layer_info": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    # snapshot / restore / fork of the simulator state (csrc/agx_snapshot.hip)
+    "agx_state_gather": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P]),
+    "agx_state_scatter": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

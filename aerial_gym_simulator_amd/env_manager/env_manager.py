@@ -64,7 +64,7 @@ class ResetSet:
 class EnvManager(BaseManager):
     def __init__(self, sim_name, env_name, robot_name, controller_name, device, args=None, num_envs=None,
                  use_warp=None, headless=None):
-        self.robot_name, self.controller_name = robot_name, controller_name
+        self.robot_name, self.controller_name, self.env_name = robot_name, controller_name, env_name
         self.sim_config = sim_config_registry.make_sim(sim_name)
         super().__init__(env_config_registry.make_env(env_name), device)
         if num_envs is not None:
@@ -852,6 +852,230 @@ class EnvManager(BaseManager):
 
     def get_obs(self):
         return self.global_tensor_dict
+
+    # ------------------------------------------------------------------ snapshot / restore / fork (snapshot.py, csrc/agx_snapshot.hip)
+    # The state of a running simulation, taken out and put back bit for bit: the per-env tensors below and the ones the owning
+    # task declares (task/base_task.py) travel through ONE table and one launch per call; the host scalars travel in the
+    # SimSnapshot.  Derived scene data (collision boxes, world triangles, BVH) is recomputed from the restored obstacle poses.
+    _state_owner = None   # the task that built this env (BaseTask._own_env_state): its tensors and counters are part of the state
+    _snap_table = None
+    _snap_error = None
+
+    def _snapshot_refusal(self):
+        """the modes whose state a snapshot would capture only in part, each named (RuntimeError), and calls inside a step"""
+        if self.post_step_launch is not None or self._in_external_simulate:
+            raise RuntimeError("snapshot() / restore() inside a step (post_step_launch is set or a plug-in robot.step() is running): "
+                               "legal only between steps, after reset() or step() has returned")
+        B = self._buffers
+        if self._lean or (B is None and self.env_args.get("lean_step")):
+            raise RuntimeError("snapshot / restore with args={'lean_step': True}: the lean step does not maintain the derived and action "
+                               "tensors a snapshot holds")
+        if (self._push is not None or (B is not None and (B.step_rows[0] or B.step_rows[1]))
+                or (B is None and getattr(self, "_step_rows", None) is not None)):
+            raise RuntimeError("snapshot / restore with bound exchange rows / peer push (sharded stepping): the rows in flight and the "
+                               "peers' sequence numbers are not part of a snapshot")
+        if getattr(self, "step_graph_mode", False):
+            raise RuntimeError("snapshot / restore with a task stepping by hipGraph replay (args={'step_graph': True}): the captured graphs "
+                               "freeze host state a restore would have to move")
+        robot = self.robot_manager.robot
+        if getattr(robot, "external_robot", False) or getattr(robot, "external_controller", False):
+            raise RuntimeError("snapshot / restore with a user-registered robot or controller class: whatever state it keeps is out of "
+                               "the package's sight")
+        if self._state_owner is not None:
+            self._state_owner._snapshot_refusal()
+
+    def snapshot_entries(self):
+        """(name, tensor, layout) of every per-env tensor the env side of the next step() reads.  The names of the first group are the
+        AgxEnvBuffers members their pointers are bound to (_bind)."""
+        g, robot, rm = self.global_tensor_dict, self.robot_manager.robot, self.robot_manager
+        mm = robot.control_allocator.motor_model
+        out = [("state", g["robot_state_soa"], "soa"), ("derived", dict.get(g, "robot_derived_soa"), "soa"),
+               ("actions", dict.get(g, "robot_actions_soa"), "soa"), ("prev_actions", dict.get(g, "robot_prev_actions_soa"), "soa"),
+               ("motor_thrust", mm.thrust_soa, "soa"), ("motor_kT", mm.kT_soa, "soa"),
+               ("motor_tau_inc", mm.tau_inc_soa, "soa"), ("motor_tau_dec", mm.tau_dec_soa, "soa"),
+               ("gains", dict.get(g, "controller_gains_soa"), "soa"),
+               ("crashes", g["crashes"], "soa"), ("truncations", g["truncations"], "soa"), ("sim_steps", g["sim_steps"], "soa"),
+               ("reset_mask", g["reset_mask"], "soa"), ("reset_flag", g["reset_flag"], "global"),
+               ("episode_count", g["episode_count"], "soa"),
+               ("bounds_min", self.bounds_soa[0], "soa"), ("bounds_max", self.bounds_soa[1], "soa"),
+               ("robot_force_tensor", dict.get(g, "robot_force_tensor"), "aos"), ("robot_torque_tensor", dict.get(g, "robot_torque_tensor"), "aos")]
+        if self.scene.num_assets > 0:  # obstacle poses; the geometry derived from them is refreshed, not stored
+            out.append(("env_asset_state_tensor", self.scene.asset_state, "aos"))
+        s = rm.warp_sensor
+        if s is not None:  # the images ARE stored: with sensor noise they are no function of the state, and the task reads them before the next render
+            out += [("depth_range_pixels", s.pixels, "aos"), ("segmentation_pixels", s.segmentation_pixels, "aos"),
+                    ("sensor_local_position", s.sensor_local_position, "aos"), ("sensor_local_orientation", s.sensor_local_orientation, "aos"),
+                    ("sensor_position", s.sensor_position, "aos"), ("sensor_orientation", s.sensor_orientation, "aos")]
+        imu = rm.imu_sensor
+        if imu is not None:
+            out += [("body_force", imu.body_force, "soa"), ("imu_bias", imu.bias, "aos"), ("imu_measurement", imu.imu_meas, "aos"),
+                    ("imu_sensor_quats", imu.sensor_quats, "aos")]
+        return out
+
+    def snapshot_table(self):
+        """the StateTable of this env and its task (built on the first call; rebuilt when a declared attribute was re-bound)"""
+        from ..snapshot import StateTable
+
+        entries = self.snapshot_entries()
+        if self._state_owner is not None:
+            entries += [("task." + name, t, layout) for name, t, layout in self._state_owner._snapshot_entries()]
+        entries = [e for e in entries if e[1] is not None and e[1].numel() > 0]
+        T = self._snap_table
+        if T is not None and len(T.entries) == len(entries) and all(c["tensor"] is e[1] for c, e in zip(T.entries, entries)):
+            return T
+        T = StateTable(self.num_envs)
+        for name, t, layout in entries:
+            T.add(name, t, layout)
+        owner = self._state_owner
+        T.fingerprint = {"abi_version": int(_lib.ABI_VERSION), "task": type(owner).__name__ if owner is not None else "",
+                         "robot": str(self.robot_name), "controller": str(self.controller_name), "env_name": str(self.env_name),
+                         "num_envs": int(self.num_envs), "env_offset": int(self.env_offset), "rng_seed": int(self.rng_seed),
+                         "layout": T.layout()}
+        self._snap_table = T
+        return T
+
+    def snapshot_fingerprint(self, table=None):
+        """what a snapshot of this simulation says about its origin (built with the table, once)"""
+        return (table or self.snapshot_table()).fingerprint
+
+    def _generators(self):
+        """(key, get, set) of every torch generator a step may draw from"""
+        dev = torch.device(self.device)
+        out = [("cpu_rng", torch.get_rng_state, torch.set_rng_state)]
+        if dev.type == "cuda":
+            out.append(("cuda_rng", lambda: torch.cuda.get_rng_state(dev), lambda s: torch.cuda.set_rng_state(s, dev)))
+        gen = getattr(self.random_source, "generator", None)
+        if gen is not None:
+            out.append(("source_rng", gen.get_state, gen.set_state))
+        return out
+
+    def _host_state(self):
+        from ..snapshot import python_random_state
+
+        h = {"step_counter": int(self.step_counter), "flag_parity": int(self._parity), "produced": ",".join(sorted(self._produced))}
+        for key, get, _set in self._generators():
+            h[key] = get().clone()
+        h.update(python_random_state())
+        return h
+
+    def _set_host_state(self, h):
+        from ..snapshot import set_python_random_state
+
+        self.step_counter = int(h["step_counter"])
+        B = self._buffers
+        B.flag_parity = int(h["flag_parity"])
+        B.step_counter = self.step_counter & 0x7FFFFFFF
+        if self._step_counter_dev is not None:
+            self._step_counter_dev.fill_(self.step_counter & 0x7FFFFFFF)
+        self._produced = set(x for x in h["produced"].split(",") if x)
+        for key, _get, set_ in self._generators():
+            if key not in h:
+                raise ValueError(f"snapshot holds no '{key}' generator state: it was taken with another random source")
+            set_(h[key])
+        set_python_random_state(h)
+
+    def snapshot(self, out=None):
+        """Everything the next step() reads, as a SimSnapshot on the device: ONE launch whatever the number of tensors, no host
+        synchronisation -- except for a navigation task in the strict_rng mode, whose three curriculum aggregates are device
+        scalars there and are read like that mode's every step reads them.  `out`: a snapshot taken earlier from this env manager,
+        overwritten in place (nothing is allocated)."""
+        from ..snapshot import SimSnapshot, first_mismatch
+
+        self._snapshot_refusal()
+        self._require_device()
+        rs = self.random_source
+        if type(rs) is not TorchRandomSource and not hasattr(rs, "generator"):
+            raise NotImplementedError(f"snapshot with random source {type(rs).__name__}: only TorchRandomSource's state can be captured")
+        T = self.snapshot_table()
+        fp = self.snapshot_fingerprint(T)
+        if out is not None:
+            bad = None if out.fingerprint is fp else first_mismatch(fp, out.fingerprint)
+            if bad is not None or out.block.device != torch.device(self.device) or tuple(out.block.shape) != (T.block_rows, self.num_envs):
+                raise ValueError(f"snapshot(out=): `out` was not taken from this env manager ({bad or 'block'} differs)")
+            snap = out
+        else:
+            snap = SimSnapshot(fp, torch.empty((T.block_rows, self.num_envs), dtype=torch.int32, device=self.device), {})
+        if self._snap_error is None:
+            self._snap_error = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.agx_state_gather(T.c_table(self._snap_error), self.num_envs, _lib.dptr(snap.block), self._stream()),
+                   "agx_state_gather")
+        owner = self._state_owner
+        snap.host = {"env": self._host_state(), "task": owner._snapshot_host() if owner is not None else {}}
+        return snap
+
+    def _restore_selection(self, env_ids, from_env_ids):
+        """(mask uint8 [N] or None, src_index int32 [N] or None) on the device.  Index env_ids are checked before anything indexes
+        with them: each in [0, N), none twice (two source rows for one env would leave the winner to chance).  A list or a CPU
+        tensor is checked on the host; a device tensor costs one host synchronisation (a mask costs none)."""
+        N, dev = self.num_envs, self.device
+        mask = ids = None
+        if env_ids is not None:
+            e = torch.as_tensor(env_ids)
+            if e.dtype in (torch.bool, torch.uint8):
+                if e.shape != (N,):
+                    raise ValueError(f"restore: a mask has shape ({N},), got {tuple(e.shape)}")
+                mask = e.to(device=dev, dtype=torch.uint8).contiguous()
+            else:
+                if e.is_floating_point() or e.is_complex():
+                    raise ValueError(f"restore: env_ids is an integer index tensor or a bool / uint8 mask, got {e.dtype}")
+                ids = e.to(torch.long).reshape(-1)
+                if ids.numel() and (bool(((ids < 0) | (ids >= N)).any()) or int(torch.unique(ids).numel()) != int(ids.numel())):
+                    raise ValueError(f"restore: env_ids must be distinct indices in [0, {N})")
+                ids = ids.to(dev)
+                mask = torch.zeros(N, dtype=torch.uint8, device=dev)
+                mask[ids] = 1
+        if from_env_ids is None:
+            return mask, None
+        f = torch.as_tensor(from_env_ids, device=dev).to(torch.int32)
+        src = torch.arange(N, dtype=torch.int32, device=dev)
+        if f.dim() == 0:  # every restored env takes this one row
+            src = f.expand(N).contiguous()
+        elif ids is not None:
+            if f.shape != ids.shape:
+                raise ValueError(f"restore: from_env_ids has {tuple(f.shape)} entries, env_ids {tuple(ids.shape)}")
+            src[ids] = f
+        else:  # all envs, or a mask: one source row per env
+            if f.shape != (N,):
+                raise ValueError(f"restore: from_env_ids without index env_ids is a scalar or has shape ({N},), got {tuple(f.shape)}")
+            src = f.contiguous()
+        return mask, src
+
+    def restore(self, snap, env_ids=None, from_env_ids=None):
+        """Put a snapshot back.  env_ids None: every env, and the global quantities with them (step counter, flag parity, generator
+        states, python's `random`, the task's counters): the steps that follow repeat, bit for bit, the ones that followed
+        snapshot().  env_ids (int64 indices, or a bool / uint8 mask): only those envs change and NO global quantity does, so they
+        replay identically only until the next random draw touches them.  from_env_ids (same length as env_ids, or one index for
+        all): the snapshot row each restored env takes -- a fork; robot and task rows move, obstacle geometry is static per env, so
+        it needs a scene without obstacles.  The device RNG stays keyed on the destination env index."""
+        from ..snapshot import first_mismatch
+
+        self._snapshot_refusal()
+        T = self.snapshot_table()
+        bad = first_mismatch(self.snapshot_fingerprint(T), snap.fingerprint)
+        if bad is not None:
+            raise ValueError(f"restore: the snapshot's '{bad}' is {snap.fingerprint.get(bad)!r}, this simulation's is "
+                             f"{self.snapshot_fingerprint(T).get(bad)!r}" if bad != "layout" else
+                             "restore: the snapshot's 'layout' (names, rows, dtypes of the packed tensors) differs from this simulation's")
+        if from_env_ids is not None and self.scene.num_assets > 0:
+            raise ValueError(f"restore(from_env_ids=...): a fork moves rows between envs, and the obstacle geometry of the {self.scene.num_assets} "
+                             "assets per env is static per env: fork needs scene.num_assets == 0 (an env without obstacles)")
+        mask, src = self._restore_selection(env_ids, from_env_ids)
+        self._require_device()
+        if self._snap_error is None:
+            self._snap_error = torch.zeros(1, dtype=torch.int32, device=self.device)
+        block = snap.block
+        if block.device != torch.device(self.device) or block.dtype != torch.int32 or not block.is_contiguous():
+            raise ValueError(f"restore: the snapshot's block lives on {block.device} ({block.dtype}); load it with SimSnapshot.from_state_dict(d, device)")
+        self._begin_call()  # whatever this step's launches had produced describes another state now; a task's single-launch proof is void
+        _lib.check(self._lib.agx_state_scatter(T.c_table(self._snap_error), self.num_envs, _lib.dptr(block), _lib.dptr(src), _lib.dptr(mask),
+                                               self._stream()), "agx_state_scatter")
+        whole = mask is None
+        if whole:
+            self._set_host_state(snap.host["env"])
+        if self.scene.num_assets > 0:  # collision boxes, world triangles, BVH of the restored envs, from their restored poses
+            self.asset_manager._refresh_geometry(self, _lib.dptr(mask))
+        if self._state_owner is not None:
+            self._state_owner._restored(snap.host.get("task", {}), whole)
 
     def delete_env(self):
         """The reference's tasks call this on close() although its EnvManager lacks it

@@ -27,6 +27,28 @@ logger = CustomLogger("navigation_task")
 class NavigationTask(BaseTask):
     _bookkeeping_fused = False  # (set by _fuse_with_env; subclasses that hand the env no task arguments leave it off)
     _bookkeeping_ptrs = None
+    # (_u_vec / _u_euler hold draws that are taken anew before every read: not state; the sensor images, mounts and poses and the
+    # obstacle poses are the env manager's)
+    SNAPSHOT_TENSORS = (("target_soa", "soa"), ("pos_err_soa", "soa"), ("prev_pos_err_soa", "soa"), ("rewards", "soa"),
+                        ("min_pixel_dist", "soa"), ("task_obs[observations]", "aos"), ("_successes", "soa"), ("_timeouts", "soa"),
+                        ("_counters", "global"))
+    SNAPSHOT_HOST = ("curriculum_level", "success_aggregate", "crashes_aggregate", "timeouts_aggregate", "num_task_steps",
+                     "_curriculum_checked_in_step")
+
+    def _snapshot_refusal(self):
+        super()._snapshot_refusal()
+        if self.vae_model is not None or self.task_config.vae_config.use_vae:
+            raise RuntimeError("snapshot / restore with vae_config.use_vae = True: the encoder's latents and workspace are not part of a snapshot")
+        if self._graph_wanted:
+            raise RuntimeError("snapshot / restore with a task stepping by hipGraph replay (args={'step_graph': True}): the captured graphs "
+                               "freeze host state a restore would have to move")
+
+    def _restored(self, host, whole):
+        super()._restored(host, whole)
+        if whole:  # what follows from the level (navigation_task.py:229-270)
+            self.obs_dict["curriculum_level"] = self.curriculum_level
+            self.obs_dict["num_obstacles_in_env"] = self.curriculum_level
+            self._update_progress()
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
         apply_overrides(task_config, seed, num_envs, headless, device, use_warp)
@@ -35,6 +57,7 @@ class NavigationTask(BaseTask):
         self.device = cfg.device
         self._args = dict(cfg.args) if isinstance(cfg.args, dict) else {}  # a snapshot: the config object is shared between tasks
         self.sim_env = build_env(cfg, cfg.args)
+        self._own_env_state()
         N, dev = self.sim_env.num_envs, self.device
         self.num_envs = N
         self.sim_env.rows_written_twice_per_step = bool(cfg.return_state_before_reset)  # see sharding.StepGather

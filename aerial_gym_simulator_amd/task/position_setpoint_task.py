@@ -13,6 +13,9 @@ logger = CustomLogger("position_setpoint_task")
 
 class PositionSetpointTask(SetpointTaskBase):
     OBSERVATION_SPACE_SHAPE = (13,)
+    # (actions / prev_actions are re-bound to the caller's tensors every step and never read: not state)
+    SNAPSHOT_TENSORS = (("target_soa", "soa"), ("rewards", "soa"), ("task_obs[observations]", "aos"), ("task_obs[collisions]", "aos"))
+    SNAPSHOT_HOST = ("counter",)
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
         # args={"lean_step": True} (opt-in, effective above 65 536 envs: EnvManager._enable_lean_step) lets the fused step stop
@@ -145,6 +148,17 @@ class PositionSetpointTask(SetpointTaskBase):
         if rc == 0 and self._strict_drew.value:
             gen.set_offset(self._strict_after.value)
         return rc
+
+    def _restored(self, host, whole):
+        super()._restored(host, whole)
+        if self._proof_watch is not None:
+            # the single-launch proof reads a record the KERNELS leave in host memory, tagged with the step index.  Steps still in
+            # flight would go on publishing records of the abandoned timeline under tags the restored step counter is about to
+            # reach again: wait for them here, once per restore.  What is in the record then carries a tag at or above the next
+            # step's and proves nothing (AGX_PROOF_TAG) until the kernels of the new timeline have published theirs.
+            torch.cuda.current_stream(self.sim_env.device).synchronize()
+            self._proof_versions = None
+            self._plan.slot_run = 0
 
     def close(self):
         if getattr(self, "_strict_word", None) is not None:

@@ -42,6 +42,11 @@ def reward_constants(name):
 
 class PositionSetpointTaskSim2RealEndToEnd(SetpointTaskBase):
     REWARD = "end_to_end"
+    # (obs_noise holds draws that are taken anew before every read: not state)
+    SNAPSHOT_TENSORS = (("target_soa", "soa"), ("rewards", "soa"), ("task_obs[observations]", "aos"), ("task_obs[collisions]", "aos"),
+                        ("actions", "aos"), ("prev_actions", "aos"), ("action_history", "aos"), ("prev_position_soa", "soa"),
+                        ("prev_pos_error_soa", "soa"))
+    SNAPSHOT_HOST = ("counter",)
 
     def __init__(self, task_config, seed=None, num_envs=None, headless=None, device=None, use_warp=None):
         logger.info("Building environment for position setpoint task.")

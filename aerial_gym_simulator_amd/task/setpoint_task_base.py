@@ -34,6 +34,7 @@ class SetpointTaskBase(BaseTask):
         cfg = self.task_config
         self.device = cfg.device
         self.sim_env = build_env(cfg, cfg.args if env_args is None else env_args)
+        self._own_env_state()
         N, dev = self.sim_env.num_envs, self.device
         self.num_envs = N
         self.actions = torch.zeros((N, cfg.action_space_dim), device=dev)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 22
+#define AGX_ABI_VERSION 23
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -1147,6 +1147,48 @@ int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pixels, int sr
  * laid out for `envs_per_chunk` envs (byte offset).                                                                       */
 int agx_vae_layer_info(const AgxVaeEncoder *enc, int layer, int envs_per_chunk, const float **w_packed, const float **bias,
                        size_t *out_offset_bytes);
+
+/* ---- snapshot / restore / fork of the simulator state (csrc/agx_snapshot.hip) ---------------------------------------------
+ * The state of a running simulation is spread over many tensors (AgxEnvBuffers, obstacle poses, sensor images and mounts,
+ * IMU bias walks, per-task tensors).  A table names them once; ONE launch packs them into a block of 32-bit words, ONE
+ * launch puts a block back -- whole, for the envs of a mask, or with every env taking the row of another env (fork).
+ *
+ * The block is [block_rows][num_envs] words; an entry of `rows` rows owns the rows * num_envs words from word
+ * block_row * num_envs on, in the order its live tensor has them:
+ *   AGX_SNAP_SOA     live [rows][N]: word r * N + env.  Lanes run along the env axis on both sides.
+ *   AGX_SNAP_AOS     live [N][rows] (images, obstacle poses): word env * rows + r.  Lanes run along the env's own words,
+ *                    which are contiguous on both sides (lanes along the env axis would stride the live side by `rows`).
+ *   AGX_SNAP_GLOBAL  live [rows], not per env (reset_flag, curriculum counters): the entry's first `rows` words; the rest of
+ *                    its rows is unused.  Written back only when every env is (mask NULL).              
+ * elem_size 4: words are copied as they are (float / int32, bits).  elem_size 1 (bool / uint8): a byte is widened to a
+ * word in the block and narrowed on the way back.  Without mask and src_index, entries whose live pointer is 16-byte
+ * aligned move 16 bytes per lane (the block side is aligned whenever num_envs % 4 == 0).                                   */
+#define AGX_SNAPSHOT_MAX_ENTRIES 96
+enum { AGX_SNAP_SOA = 0, AGX_SNAP_AOS = 1, AGX_SNAP_GLOBAL = 2 };
+typedef struct {
+  void *ptr;          /* device, live tensor                                                                               */
+  int32_t rows;       /* > 0; rows * num_envs < 2^31                                                                        */
+  int32_t block_row;  /* first row of this entry in the block: the sum of `rows` of the entries before it                   */
+  int32_t elem_size;  /* 1 or 4 bytes                                                                                       */
+  int32_t layout;     /* AGX_SNAP_*                                                                                         */
+} AgxSnapshotEntry;
+typedef struct {
+  int32_t count;        /* entries in use, 1 .. AGX_SNAPSHOT_MAX_ENTRIES                                                    */
+  int32_t block_rows;   /* sum of rows                                                                                      */
+  uint32_t *error;      /* device [1], zero: set to 1 by a scatter that met an out-of-range src_index entry                 */
+  AgxSnapshotEntry entry[AGX_SNAPSHOT_MAX_ENTRIES];
+} AgxSnapshotTable;
+/* block <- live tensors.  One launch, no host synchronisation.                                                             */
+int agx_state_gather(const AgxSnapshotTable *table, int num_envs, void *block, void *stream);
+/* live[row][env] <- block[row][src_index[env]] where mask[env] != 0.  src_index (int32 [N], device; NULL: identity), mask
+ * (uint8 [N], device; NULL: every env).  One launch.  Every wave range-checks ALL of src_index before it stores anything:
+ * with an entry outside [0, N) nothing is written, nothing is read out of bounds and table->error becomes 1.  With
+ * src_index the call then waits for the stream, reads the word, clears it and returns AGX_E_ARG when it was set (a fork is
+ * a planner's branch point, not a per-step call); without src_index it does not synchronise.  Cost of the check: every wave
+ * of the launch reads all N indices (N / 64 loads per wave, served from L2 after the first); with large AoS entries (images)
+ * at thousands of envs that is millions of redundant loads per fork.  Not measured.                                        */
+int agx_state_scatter(const AgxSnapshotTable *table, int num_envs, const void *block, const int32_t *src_index,
+                      const uint8_t *mask, void *stream);
 
 #ifdef __cplusplus
 }
