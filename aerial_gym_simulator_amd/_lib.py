@@ -307,6 +307,9 @@ class AgxVaeConv(C.Structure):
 VAE_ELU, VAE_LAYERS, MATH_EXPM1 = 1, 11, 5  # AGX_VAE_ELU, AGX_VAE_LAYERS, AGX_MATH_EXPM1
 
 SNAPSHOT_MAX_ENTRIES = 96  # AGX_SNAPSHOT_MAX_ENTRIES
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 8, 512  # AGX_POLICY_MAX_LAYERS, AGX_POLICY_MAX_WIDTH
+POLICY_NONE, POLICY_ELU, POLICY_RELU = 0, 1, 2  # AGX_POLICY_NONE / _ELU / _RELU
+POLICY_SAMPLE, POLICY_CLAMP = 1, 2  # AGX_POLICY_SAMPLE / _CLAMP
 SNAP_SOA, SNAP_AOS, SNAP_GLOBAL = 0, 1, 2  # AGX_SNAP_*
 
 
@@ -319,7 +322,7 @@ class AgxSnapshotTable(C.Structure):
     _fields_ = [("count", C.c_int32), ("block_rows", C.c_int32), ("error", C.c_void_p), ("entry", AgxSnapshotEntry * SNAPSHOT_MAX_ENTRIES)]
 
 
-ABI_VERSION = 23  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 24  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -478,6 +481,14 @@ _SIGNATURES = {
     # snapshot / restore / fork of the simulator state (csrc/agx_snapshot.hip)
     "agx_state_gather": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P]),
     "agx_state_scatter": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P, _P, _P]),
+    # policy actor (csrc/agx_policy.hip)
+    "agx_policy_check": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "agx_policy_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    "agx_policy_set_input_norm": (C.c_int, [_P, _P, _P, C.c_float]),
+    "agx_policy_set_logstd": (C.c_int, [_P, _P]),
+    "agx_policy_act": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P]),
+    "agx_policy_noise": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P, _P]),
+    "agx_policy_destroy": (C.c_int, [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

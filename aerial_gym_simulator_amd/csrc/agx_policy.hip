@@ -1,0 +1,369 @@
+// Actor MLP of a trained policy (examples/rl_games_example/rl_games_inference.py:7-48 and what rl_games' player does around it:
+// input normalisation, sampling, clamping) as ONE launch.  DESIGN.md "Policy actor".
+//
+// A workgroup of four waves owns a tile of 32 envs: the B column of v_mfma_f32_32x32x2_f32.  The activations of the tile live in
+// LDS as [width][32] (env on the fast axis), ping-ponging between two buffers; they never go to memory.  Per layer the waves
+// split the output channels in tiles of 32 (wave w: tiles w, w + 4, w + 8, w + 12); a wave runs the k loop of csrc/agx_vae.hip
+// on its tiles: lane l supplies A = W[co = l & 31][k0 + (l >> 5)] from the packed [K8][Cout] weights and B = X[k0 + (l >> 5)][env =
+// l & 31] from LDS, the hardware adds the two products in k order.  An output is therefore the fmaf chain k = 0, 1, 2, ... from 0,
+// then + bias, then the activation -- the bits of agx_vae_linear applied layer by layer, whatever the batch, the env's place in
+// it or the number of tiles a wave holds.  Weights stream from L2 four chunks of 8 k ahead of the instructions that use them.
+#include "agx_common.h"
+#include "agx_device_math.h"
+#include "agx_rng.h"
+#include "agx_task_parts.h"
+
+#include <vector>
+
+namespace {
+using namespace agx;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kWaves = 4;
+constexpr int kTile = 32;                                    // envs per workgroup
+static_assert(AGX_POLICY_MAX_WIDTH / 32 <= 4 * kWaves, "a wave holds at most four channel tiles (layer_tiles<1 .. 4>)");
+constexpr size_t kLdsLimit = 160 * 1024;
+
+struct PolicyK {
+  const float *w[AGX_POLICY_MAX_LAYERS];  // packed [k8][cout]
+  const float *b[AGX_POLICY_MAX_LAYERS];  // [cout]
+  int k8[AGX_POLICY_MAX_LAYERS];          // rows of the packed weights = width of the layer's input in LDS
+  int cout[AGX_POLICY_MAX_LAYERS];        // multiple of 32 (the last layer padded)
+  int num_layers, in_dim, out_dim, activation;
+  const float *obs, *eps, *logstd, *mean, *denom;
+  float *actions, *mu_out;
+  float clip;
+  int n, flags, env_base, step;
+  int buf1;  // first float of the second activation buffer
+  uint64_t seed;
+};
+
+// normal j of env `genv` at env step `step`: the pairing of vae_normal (agx_vae.hip) under its own stream id
+AGX_DEV float policy_normal(uint64_t seed, int genv, int step, int j) {
+  const F4 f = rng_block(seed, genv, step, RNG_POLICY_EPS, j >> 2);
+  const int e = j & 2;
+  float z0, z1;
+  normal_pair(e ? f.v[2] : f.v[0], e ? f.v[3] : f.v[1], z0, z1);
+  return (j & 1) ? z1 : z0;
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kRing = 5;          // chunks of 8 k a wave holds: one in use, kAhead in flight
+constexpr int kAhead = kRing - 1;
+
+template <int NT>
+AGX_DEV void load_chunk(float (&dst)[4][NT], const float *__restrict__ wl, int k0, int cout) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dst[u][t] = wl[(size_t)(k0 + 2 * u) * (size_t)cout + (size_t)(32 * kWaves * t)];
+}
+
+template <int NT>
+AGX_DEV void mfma_chunk(f32x16 (&acc)[NT], const float (&wv)[4][NT], const float *__restrict__ xl, int k0) {
+  float b[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) b[u] = xl[(k0 + 2 * u) * kTile];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u][t], b[u], acc[t], 0, 0, 0);
+}
+
+// one layer for the NT channel tiles of this wave: tiles wave, wave + 4, ...
+template <int NT>
+AGX_DEV void layer_tiles(const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ x, float *__restrict__ y,
+                         int k8, int cout, int activation, int wave, int lane) {
+  const int col = lane & 31, half = lane >> 5;
+  const float *__restrict__ wl = w + (size_t)half * (size_t)cout + (size_t)(32 * wave + col);
+  const float *__restrict__ xl = x + half * kTile + col;
+  // result register i of lane l: channel (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the 32, env l & 31.  The biases of a lane's sixteen
+  // channels are four runs of four: fetched here, in front of the k loop, not one by one behind it
+  f32x4 bv[NT][4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bv[t][q] = *(const f32x4 *)(bias + 32 * (wave + kWaves * t) + 8 * q + 4 * half);
+  f32x16 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+  // a ring of chunks of 8 k: kAhead in flight while one is used.  The main loop is one basic block (the ring index is a
+  // compile-time constant in it), so the compiler counts the loads in flight instead of waiting for all of them.  A chunk past the
+  // end re-reads the last one (in bounds).
+  float ring[kRing][4][NT];
+  const int chunks = k8 >> 3, last = k8 - 8;
+#pragma unroll
+  for (int s = 0; s < kAhead; ++s) load_chunk<NT>(ring[s], wl, min(8 * s, last), cout);
+  int c = 0;
+  for (; c + kRing <= chunks; c += kRing) {
+#pragma unroll
+    for (int s = 0; s < kRing; ++s) {
+      load_chunk<NT>(ring[(s + kAhead) % kRing], wl, min(8 * (c + s + kAhead), last), cout);
+      mfma_chunk<NT>(acc, ring[s], xl, 8 * (c + s));
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < kRing - 1; ++s) {
+    if (c + s < chunks) {
+      if (c + s + kAhead < chunks) load_chunk<NT>(ring[(s + kAhead) % kRing], wl, 8 * (c + s + kAhead), cout);
+      mfma_chunk<NT>(acc, ring[s], xl, 8 * (c + s));
+    }
+  }
+  float v[NT][16];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[t][i] = acc[t][i] + bv[t][i >> 2][i & 3];
+  if (activation == AGX_POLICY_ELU) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[t][i] = (v[t][i] > 0.0f) ? v[t][i] : expm1_cw(v[t][i]);
+  } else if (activation == AGX_POLICY_RELU) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[t][i] = (v[t][i] < 0.0f) ? 0.0f : v[t][i];
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) y[(32 * (wave + kWaves * t) + (i & 3) + 8 * (i >> 2) + 4 * half) * kTile + col] = v[t][i];
+}
+
+__global__ void __launch_bounds__(64 * kWaves) k_policy_act(PolicyK a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long env0 = (long long)blockIdx.x * kTile;
+  const int live = (int)min((long long)kTile, (long long)a.n - env0);  // envs of this tile, 1 .. 32
+  // ---- the observations, transposed into [k8][32]; dead envs and the k padding are zero ----
+  {
+    float *__restrict__ x0 = lds;
+    const float *__restrict__ src = a.obs + (size_t)env0 * (size_t)a.in_dim;
+    const int k8 = a.k8[0];
+    for (int i = tid; i < kTile * k8; i += 64 * kWaves) {
+      // lanes run along the envs: LDS words in order (lanes along k would all hit one bank); the 32 rows a load instruction
+      // touches are one contiguous piece of obs, and the next k reads the same cache lines
+      const int k = i >> 5, col = i & 31;
+      float v = 0.0f;
+      if (col < live && k < a.in_dim) {
+        v = src[(size_t)col * (size_t)a.in_dim + (size_t)k];
+        if (a.mean) {
+          v = (v - a.mean[k]) / a.denom[k];
+          v = (v < -a.clip) ? -a.clip : ((v > a.clip) ? a.clip : v);
+        }
+      }
+      x0[k * kTile + col] = v;
+    }
+  }
+  __syncthreads();
+  // ---- the layers ----
+  for (int l = 0; l < a.num_layers; ++l) {
+    const float *__restrict__ x = lds + ((l & 1) ? a.buf1 : 0);
+    float *__restrict__ y = lds + ((l & 1) ? 0 : a.buf1);
+    const int cout = a.cout[l], tiles = cout >> 5;
+    const int nt = wave < tiles ? (tiles - wave + kWaves - 1) / kWaves : 0;  // wave-uniform
+    const int act = (l + 1 < a.num_layers) ? a.activation : AGX_POLICY_NONE;
+    if (nt == 1) layer_tiles<1>(a.w[l], a.b[l], x, y, a.k8[l], cout, act, wave, lane);
+    else if (nt == 2) layer_tiles<2>(a.w[l], a.b[l], x, y, a.k8[l], cout, act, wave, lane);
+    else if (nt == 3) layer_tiles<3>(a.w[l], a.b[l], x, y, a.k8[l], cout, act, wave, lane);
+    else if (nt == 4) layer_tiles<4>(a.w[l], a.b[l], x, y, a.k8[l], cout, act, wave, lane);
+    __syncthreads();
+  }
+  // ---- mean -> (sample) -> (clamp) -> [N][out], rows of the tile contiguous ----
+  const float *__restrict__ mu_t = lds + ((a.num_layers & 1) ? a.buf1 : 0);
+  const size_t out0 = (size_t)env0 * (size_t)a.out_dim;
+  for (int i = tid; i < live * a.out_dim; i += 64 * kWaves) {
+    const int col = i / a.out_dim, j = i - col * a.out_dim;
+    const float mu = mu_t[j * kTile + col];
+    float v = mu;
+    if (a.flags & AGX_POLICY_SAMPLE) {
+      const float sigma = exp_cw(a.logstd[j]);
+      const float e = a.eps ? a.eps[out0 + i] : policy_normal(a.seed, a.env_base + (int)env0 + col, a.step, j);
+      const float t = e * sigma;
+      v = mu + t;
+    }
+    if (a.flags & AGX_POLICY_CLAMP) v = (v < -1.0f) ? -1.0f : ((v > 1.0f) ? 1.0f : v);
+    a.actions[out0 + i] = v;
+    if (a.mu_out) a.mu_out[out0 + i] = mu;
+  }
+}
+
+__global__ void k_policy_noise(int n, int out_dim, uint64_t seed, int env_base, int step, float *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)n * out_dim) return;
+  const int env = (int)(i / out_dim);
+  out[i] = policy_normal(seed, env_base + env, step, (int)(i - (long long)env * out_dim));
+}
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+}  // namespace
+
+struct AgxPolicy {
+  int num_layers, activation;
+  int dims[AGX_POLICY_MAX_LAYERS + 1];
+  int k8[AGX_POLICY_MAX_LAYERS], cout[AGX_POLICY_MAX_LAYERS];
+  float *w[AGX_POLICY_MAX_LAYERS], *b[AGX_POLICY_MAX_LAYERS];
+  float *mean, *denom, *logstd;  // device, allocated by create; in use once set
+  bool has_norm, has_logstd;
+  float clip;
+  int buf1;
+  size_t lds_bytes;
+};
+
+extern "C" int agx_policy_destroy(AgxPolicy *p) {
+  if (!p) return AGX_OK;
+  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) {
+    if (p->w[l]) (void)hipFree(p->w[l]);
+    if (p->b[l]) (void)hipFree(p->b[l]);
+  }
+  if (p->mean) (void)hipFree(p->mean);
+  if (p->denom) (void)hipFree(p->denom);
+  if (p->logstd) (void)hipFree(p->logstd);
+  delete p;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_check(int num_layers, const int32_t *dims, size_t *lds_bytes) {
+  AGX_REQUIRE(dims, "agx_policy_create: null dims");
+  AGX_REQUIRE(num_layers >= 1 && num_layers <= AGX_POLICY_MAX_LAYERS, "agx_policy_create: num_layers = %d, supported: 1 .. %d", num_layers,
+              AGX_POLICY_MAX_LAYERS);
+  AGX_REQUIRE(dims[0] >= 1 && dims[0] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: input width %d, supported: 1 .. %d", dims[0],
+              AGX_POLICY_MAX_WIDTH);
+  for (int l = 1; l < num_layers; ++l)
+    AGX_REQUIRE(dims[l] >= 32 && dims[l] <= AGX_POLICY_MAX_WIDTH && dims[l] % 32 == 0,
+                "agx_policy_create: hidden width %d (output of layer %d): a multiple of 32 up to %d is supported", dims[l], l - 1,
+                AGX_POLICY_MAX_WIDTH);
+  AGX_REQUIRE(dims[num_layers] >= 1 && dims[num_layers] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: output width %d, supported: 1 .. %d",
+              dims[num_layers], AGX_POLICY_MAX_WIDTH);
+  // activation a (0 = the input .. num_layers = the mean) lives in buffer a & 1
+  int width[2] = {0, 0};
+  for (int a = 0; a <= num_layers; ++a) {
+    const int wa = a == 0 ? round_up(dims[0], 8) : (a == num_layers ? round_up(dims[a], 32) : dims[a]);
+    if (wa > width[a & 1]) width[a & 1] = wa;
+  }
+  const size_t bytes = (size_t)(width[0] + width[1]) * kTile * sizeof(float);
+  AGX_REQUIRE(bytes <= kLdsLimit, "agx_policy_create: activations of widths %d + %d for 32 envs need %zu bytes of LDS, a workgroup has %zu",
+              width[0], width[1], bytes, kLdsLimit);
+  if (lds_bytes) *lds_bytes = bytes;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_create(int num_layers, const int32_t *dims, const float *const *weights, const float *const *biases,
+                                 int hidden_activation, AgxPolicy **out) {
+  AGX_REQUIRE(out, "agx_policy_create: null handle pointer");
+  *out = nullptr;
+  AGX_REQUIRE(dims && weights && biases, "agx_policy_create: null argument");
+  size_t lds_bytes = 0;
+  if (int e = agx_policy_check(num_layers, dims, &lds_bytes)) return e;
+  AGX_REQUIRE(hidden_activation == AGX_POLICY_NONE || hidden_activation == AGX_POLICY_ELU || hidden_activation == AGX_POLICY_RELU,
+              "agx_policy_create: hidden_activation = %d (AGX_POLICY_NONE, _ELU or _RELU)", hidden_activation);
+  for (int l = 0; l < num_layers; ++l) AGX_REQUIRE(weights[l] && biases[l], "agx_policy_create: layer %d: null weight or bias", l);
+  AgxPolicy *p = new AgxPolicy();
+  p->num_layers = num_layers;
+  p->activation = hidden_activation;
+  for (int l = 0; l <= num_layers; ++l) p->dims[l] = dims[l];
+  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) { p->w[l] = p->b[l] = nullptr; p->k8[l] = p->cout[l] = 0; }
+  p->mean = p->denom = p->logstd = nullptr;
+  p->has_norm = p->has_logstd = false;
+  p->clip = 0.0f;
+  p->lds_bytes = lds_bytes;
+  int width0 = 0;
+  for (int a = 0; a <= num_layers; a += 2) {
+    const int wa = a == 0 ? round_up(dims[0], 8) : (a == num_layers ? round_up(dims[a], 32) : dims[a]);
+    if (wa > width0) width0 = wa;
+  }
+  p->buf1 = width0 * kTile;
+  hipError_t e = hipSuccess;
+  for (int l = 0; l < num_layers && e == hipSuccess; ++l) {
+    const int k = dims[l], co = dims[l + 1];
+    const int cop = l + 1 == num_layers ? round_up(co, 32) : co;
+    p->k8[l] = round_up(k, 8);
+    p->cout[l] = cop;
+    // the last layer's rows past `co` are zero weights and zero biases: padding the caller never sees
+    std::vector<float> padded((size_t)cop * k, 0.0f), bias((size_t)cop, 0.0f);
+    for (size_t i = 0; i < (size_t)co * k; ++i) padded[i] = weights[l][i];
+    for (int i = 0; i < co; ++i) bias[i] = biases[l][i];
+    std::vector<float> packed(agx_vae_packed_floats(cop, k));
+    agx_vae_pack_weight(cop, k, padded.data(), packed.data());
+    e = hipMalloc((void **)&p->w[l], packed.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&p->b[l], bias.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc((void **)&p->mean, (size_t)dims[0] * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&p->denom, (size_t)dims[0] * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&p->logstd, (size_t)dims[num_layers] * sizeof(float));
+  // above 64 KiB of dynamic LDS the runtime may want to be told; a runtime that refuses the attribute refuses the launch too,
+  // and says so there
+  if (e == hipSuccess && lds_bytes > 64 * 1024) {
+    (void)hipFuncSetAttribute((const void *)k_policy_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    (void)hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    agx_policy_destroy(p);
+    (void)hipGetLastError();
+    return fail(AGX_E_LAUNCH, "agx_policy_create: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_set_input_norm(AgxPolicy *p, const float *mean, const float *denom, float clip) {
+  AGX_REQUIRE(p, "agx_policy_set_input_norm: null handle");
+  if (!mean && !denom) { p->has_norm = false; return AGX_OK; }
+  AGX_REQUIRE(mean && denom, "agx_policy_set_input_norm: mean and denom come together");
+  AGX_REQUIRE(clip > 0.0f, "agx_policy_set_input_norm: clip = %g must be positive", (double)clip);
+  hipError_t e = hipMemcpy(p->mean, mean, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->denom, denom, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_policy_set_input_norm: %s", hipGetErrorString(e));
+  p->clip = clip;
+  p->has_norm = true;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_set_logstd(AgxPolicy *p, const float *logstd) {
+  AGX_REQUIRE(p, "agx_policy_set_logstd: null handle");
+  if (!logstd) { p->has_logstd = false; return AGX_OK; }
+  hipError_t e = hipMemcpy(p->logstd, logstd, (size_t)p->dims[p->num_layers] * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_policy_set_logstd: %s", hipGetErrorString(e));
+  p->has_logstd = true;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_act(AgxPolicy *p, int num_envs, const float *obs, float *actions, float *mu_out, const float *eps, int flags,
+                              uint64_t rng_seed, int env_index_base, int env_step, void *stream) {
+  AGX_REQUIRE(p, "agx_policy_act: null handle");
+  AGX_REQUIRE(num_envs >= 0 && num_envs <= (1 << 22), "agx_policy_act: num_envs = %d, supported: 0 .. %d", num_envs, 1 << 22);
+  AGX_REQUIRE((flags & ~(AGX_POLICY_SAMPLE | AGX_POLICY_CLAMP)) == 0, "agx_policy_act: flags = %d", flags);
+  AGX_REQUIRE(!(flags & AGX_POLICY_SAMPLE) || p->has_logstd, "agx_policy_act: AGX_POLICY_SAMPLE needs a logstd (agx_policy_set_logstd)");
+  if (num_envs == 0) return AGX_OK;
+  AGX_REQUIRE(obs, "agx_policy_act: null obs");
+  AGX_REQUIRE(actions, "agx_policy_act: null actions");
+  PolicyK a;
+  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) { a.w[l] = p->w[l]; a.b[l] = p->b[l]; a.k8[l] = p->k8[l]; a.cout[l] = p->cout[l]; }
+  a.num_layers = p->num_layers; a.in_dim = p->dims[0]; a.out_dim = p->dims[p->num_layers]; a.activation = p->activation;
+  a.obs = obs; a.eps = eps; a.logstd = p->logstd;
+  a.mean = p->has_norm ? p->mean : nullptr; a.denom = p->has_norm ? p->denom : nullptr;
+  a.actions = actions; a.mu_out = mu_out;
+  a.clip = p->clip;
+  a.n = num_envs; a.flags = flags; a.env_base = env_index_base; a.step = env_step;
+  a.buf1 = p->buf1;
+  a.seed = rng_seed;
+  hipLaunchKernelGGL(k_policy_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->lds_bytes, (hipStream_t)stream, a);
+  return check_launch("agx_policy_act");
+}
+
+extern "C" int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                                void *stream) {
+  AGX_REQUIRE(p && noise_out, "agx_policy_noise: null argument");
+  AGX_REQUIRE(num_envs > 0 && num_envs <= (1 << 22), "agx_policy_noise: num_envs = %d, supported: 1 .. %d", num_envs, 1 << 22);
+  const int out_dim = p->dims[p->num_layers];
+  const long long total = (long long)num_envs * out_dim;
+  hipLaunchKernelGGL(k_policy_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, out_dim, rng_seed,
+                     env_index_base, env_step, noise_out);
+  return check_launch("agx_policy_noise");
+}

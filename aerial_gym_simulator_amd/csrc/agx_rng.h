@@ -37,6 +37,7 @@ enum {
   RNG_RADAR_NOISE = 11,  // counter word 1 = env step; block = pooled cell       (agx_radar_image_obs)
   RNG_VAE_EPS = 12,     // counter word 1 = env step; 16 blocks -> 64 uniforms -> 32 Box-Muller pairs: normals (2 p, 2 p + 1) from
                         // uniforms (2 p, 2 p + 1)                                (agx_vae_sample, agx_vae_noise)
+  RNG_POLICY_EPS = 13,  // counter word 1 = env step; block = action index / 4; the pairing of RNG_VAE_EPS (agx_policy_act, agx_policy_noise)
   RNG_ASSETS = 16,      // + asset index (< 2^16 assets)
   RNG_SENSOR_MOUNT = 1 << 16,  // + sensor index; counter word 1 = episode; 6 draws  (agx_sensor_mount_reset)
   RNG_DISTURB = 1 << 20 // + sub-step; counter word 1 = env step

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 23
+#define AGX_ABI_VERSION 24
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -1189,6 +1189,51 @@ int agx_state_gather(const AgxSnapshotTable *table, int num_envs, void *block, v
  * at thousands of envs that is millions of redundant loads per fork.  Not measured.                                        */
 int agx_state_scatter(const AgxSnapshotTable *table, int num_envs, const void *block, const int32_t *src_index,
                       const uint8_t *mask, void *stream);
+
+/* ---- policy actor: a trained MLP in the loop as one launch (csrc/agx_policy.hip) -------------------------------------------
+ * Replaces the torch module of examples/rl_games_example/rl_games_inference.py:7-48 (MLP: Linear / ELU x 3, Linear) and, for
+ * input normalisation, sampling and clamping, what rl_games' player does around it (players.py PpoPlayerContinuous.get_action:
+ * running_mean_std, mu + sigma * randn, clamp to [-1, 1]; common/player.py BasePlayer).  DESIGN.md "Policy actor".
+ *
+ * Numerics: every layer output is ONE fmaf chain over k = 0, 1, 2, ... starting from 0 (v_mfma_f32_32x32x2_f32), then + bias,
+ * then the activation -- each a rounded fp32 operation: the bits of agx_vae_linear applied layer by layer.  The result does not
+ * depend on the batch size, the env's position in the batch or how the waves split the channels.
+ *
+ * Limits: 1 .. AGX_POLICY_MAX_LAYERS layers; input width 1 .. AGX_POLICY_MAX_WIDTH; hidden widths multiples of 32 up to
+ * AGX_POLICY_MAX_WIDTH; output width 1 .. AGX_POLICY_MAX_WIDTH; the activations of 32 envs of any two consecutive layers fit the
+ * 160 KiB of LDS of a workgroup.  Outside them: AGX_E_ARG, the message names the offending number.                          */
+#define AGX_POLICY_MAX_LAYERS 8
+#define AGX_POLICY_MAX_WIDTH 512
+enum { AGX_POLICY_NONE = 0, AGX_POLICY_ELU = 1 /* alpha 1, expm1_cw on the negative side */, AGX_POLICY_RELU = 2 };
+enum { AGX_POLICY_SAMPLE = 1, AGX_POLICY_CLAMP = 2 };  /* flags of the act call */
+typedef struct AgxPolicy AgxPolicy;
+/* Host only: the limits above for dims [num_layers + 1] (what the create call checks first); lds_bytes (optional) receives the
+ * dynamic LDS of the launch.                                                                                                */
+int agx_policy_check(int num_layers, const int32_t *dims, size_t *lds_bytes);
+/* weights / biases: num_layers HOST pointers each, torch's [out][in] and [out].  hidden_activation: AGX_POLICY_NONE / _ELU /
+ * _RELU after every layer but the last (mu_activation None in both rl_games recipes).  The handle owns the repacked device
+ * copies ([K8][Cout] as the VAE's, the last layer padded to a multiple of 32 zero rows the caller never sees) and the buffers
+ * the two setters fill.  Create, the setters and destroy are the set-up calls: they copy from host memory and wait for the
+ * copy; only create and destroy allocate and free.                                                                          */
+int agx_policy_create(int num_layers, const int32_t *dims, const float *const *weights, const float *const *biases,
+                      int hidden_activation, AgxPolicy **out);
+/* rl_games' normalize_input (running_mean_std.py RunningMeanStd.forward): before layer 0 the kernel computes
+ * clamp((x - mean) / denom, -clip, clip) with IEEE subtraction and division.  mean, denom: HOST [in]; the caller computes
+ * denom = sqrt(var + 1e-5) in float32.  Both NULL: switched off again.                                                        */
+int agx_policy_set_input_norm(AgxPolicy *p, const float *mean, const float *denom, float clip);
+/* logstd: HOST [out], the per-action `sigma` parameter of the checkpoint (fixed_sigma).  NULL: none.                         */
+int agx_policy_set_logstd(AgxPolicy *p, const float *logstd);
+/* obs [N][in] -> actions [N][out] (device): one launch, no allocation, no host synchronisation, no host randomness.
+ * mu_out (optional, [N][out]): the mean before sampling and clamping.  AGX_POLICY_SAMPLE: sigma = exp_cw(logstd), t = eps *
+ * sigma, a = mu + t, each rounded; eps [N][out], or NULL = the device generator: standard normals that are a function of
+ * (rng_seed, env_index_base + env, env_step, action index) alone (RNG_POLICY_EPS).  AGX_POLICY_CLAMP: clip to [-1, 1], last.
+ * num_envs = 0 does nothing.                                                                                                */
+int agx_policy_act(AgxPolicy *p, int num_envs, const float *obs, float *actions, float *mu_out, const float *eps, int flags,
+                   uint64_t rng_seed, int env_index_base, int env_step, void *stream);
+/* Diagnostic: noise_out [N][out] <- the normals the NULL-eps form draws.                                                     */
+int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                     void *stream);
+int agx_policy_destroy(AgxPolicy *p);
 
 #ifdef __cplusplus
 }
