@@ -309,7 +309,8 @@ VAE_ELU, VAE_LAYERS, MATH_EXPM1 = 1, 11, 5  # AGX_VAE_ELU, AGX_VAE_LAYERS, AGX_M
 SNAPSHOT_MAX_ENTRIES = 96  # AGX_SNAPSHOT_MAX_ENTRIES
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 8, 512  # AGX_POLICY_MAX_LAYERS, AGX_POLICY_MAX_WIDTH
 POLICY_NONE, POLICY_ELU, POLICY_RELU = 0, 1, 2  # AGX_POLICY_NONE / _ELU / _RELU
-POLICY_SAMPLE, POLICY_CLAMP = 1, 2  # AGX_POLICY_SAMPLE / _CLAMP
+POLICY_SAMPLE, POLICY_CLAMP, POLICY_RESET_AFTER = 1, 2, 4  # AGX_POLICY_SAMPLE / _CLAMP / _RESET_AFTER
+MATH_SIGMOID, MATH_TANH = 6, 7  # AGX_MATH_SIGMOID, AGX_MATH_TANH
 SNAP_SOA, SNAP_AOS, SNAP_GLOBAL = 0, 1, 2  # AGX_SNAP_*
 
 
@@ -322,7 +323,7 @@ class AgxSnapshotTable(C.Structure):
     _fields_ = [("count", C.c_int32), ("block_rows", C.c_int32), ("error", C.c_void_p), ("entry", AgxSnapshotEntry * SNAPSHOT_MAX_ENTRIES)]
 
 
-ABI_VERSION = 24  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
+ABI_VERSION = 25  # AGX_ABI_VERSION of include/aerial_gym_hip.h these mirrors were written against
 _P = C.c_void_p
 _SIGNATURES = {
     "agx_last_error": (C.c_char_p, []),
@@ -489,6 +490,15 @@ _SIGNATURES = {
     "agx_policy_act": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P]),
     "agx_policy_noise": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P, _P]),
     "agx_policy_destroy": (C.c_int, [_P]),
+    # recurrent actor (csrc/agx_policy.hip)
+    "agx_recurrent_check": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "agx_recurrent_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_void_p)]),
+    "agx_recurrent_set_input_norm": (C.c_int, [_P, _P, _P, C.c_float]),
+    "agx_recurrent_set_logstd": (C.c_int, [_P, _P]),
+    "agx_recurrent_act": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P]),
+    "agx_recurrent_noise": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_int, C.c_int, _P, _P]),
+    "agx_recurrent_destroy": (C.c_int, [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -262,6 +262,50 @@ AGX_DEV float expm1_cw(float x) {
   const double two_k = __longlong_as_double((long long)(k + 1023) << 52);  // 2^k, -151 <= k <= 128
   return (float)fmad(two_k, q, two_k - 1.0);
 }
+// The gates of a recurrent cell (agx_policy.hip k_recurrent_act).  Both stay in float64 from the reduction to the one rounding:
+// exp_cw's reduction x = k ln2 + r and polynomial, then one division.
+// q = e^r - 1 = r + r^2 p(r) and k of x = k ln2 + r, |x| < 700
+AGX_DEV double expm1_reduced(double xd, int &k) {
+  const double kd = __builtin_rint(xd * kInvLn2);
+  k = (int)kd;
+  double r = fmad(-kd, kLn2Hi, xd);
+  r = fmad(-kd, kLn2Lo, r);
+  double p = 0x1.288088c0e67a5p-22;
+  p = fmad(p, r, 0x1.72c79824255e0p-19);
+  p = fmad(p, r, 0x1.a019c971b4d98p-16);
+  p = fmad(p, r, 0x1.a019ad55d1aa7p-13);
+  p = fmad(p, r, 0x1.6c16c1739a511p-10);
+  p = fmad(p, r, 0x1.1111111c5719ap-7);
+  p = fmad(p, r, 0x1.5555555554ca7p-5);
+  p = fmad(p, r, 0x1.5555555553b48p-3);
+  p = fmad(p, r, 0x1.0000000000000p-1);
+  return fmad(r * r, p, r);
+}
+// sigmoid = 1 / (1 + e^-x) with e^-x = 2^k (1 + q).  Above 20, e^-x < 2^-28 is far under half an ulp of 1: exactly 1.  Below
+// exp_cw's flush threshold the value (e^x to within 2^-126 relative) is under the smallest normal float: 0, exp_cw's convention.
+AGX_DEV float sigmoid_cw(float x) {
+  if (x > 20.0f) return 1.0f;
+  if (x < -87.3365402f) return 0.0f;
+  int k;
+  const double q = expm1_reduced(-(double)x, k);
+  const double two_k = __longlong_as_double((long long)(k + 1023) << 52);  // 2^k, -29 <= k <= 126
+  const double e = (1.0 + q) * two_k;
+  return (float)(1.0 / (1.0 + e));
+}
+// tanh = -t / (t + 2) with t = expm1(-2 |x|) in (-1, 0]: t + 2 lies in (1, 2], nothing cancels; t as in expm1_cw.  Below 2^-14
+// the series x - x^3 / 3 differs from x by less than 2^-29 relative, far under half an ulp: x itself, signed zeros included.
+// Above 10, 1 - tanh < 2 e^-20 is under a quarter ulp of 1: exactly +-1.
+AGX_DEV float tanh_cw(float x) {
+  const float ax = fabsf(x);
+  if (ax < 0x1p-14f) return x;
+  if (ax > 10.0f) return (x < 0.0f) ? -1.0f : 1.0f;
+  int k;
+  const double q = expm1_reduced(-2.0 * (double)ax, k);
+  const double two_k = __longlong_as_double((long long)(k + 1023) << 52);  // 2^k, -29 <= k <= 0
+  const double t = (k == 0) ? q : fmad(two_k, q, two_k - 1.0);
+  const double v = -t / (t + 2.0);
+  return (float)((x < 0.0f) ? -v : v);
+}
 
 // utils/math.py:156-172
 AGX_DEV Q4 quat_from_euler(float roll, float pitch, float yaw) {

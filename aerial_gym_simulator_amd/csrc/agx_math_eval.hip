@@ -17,6 +17,8 @@ __global__ void k_math_eval(int which, int n, const float *__restrict__ x, const
     case AGX_MATH_ATAN2: out[i] = atan2_cw(x[i], y[i]); break;
     case AGX_MATH_ASIN: out[i] = asin_cw(x[i]); break;
     case AGX_MATH_EXPM1: out[i] = expm1_cw(x[i]); break;
+    case AGX_MATH_SIGMOID: out[i] = sigmoid_cw(x[i]); break;
+    case AGX_MATH_TANH: out[i] = tanh_cw(x[i]); break;
     default: out[i] = exp_cw(x[i]); break;
   }
 }
@@ -41,7 +43,7 @@ extern "C" int agx_copy_f4(const void *src, void *dst, size_t bytes, void *strea
 }
 
 extern "C" int agx_math_eval(int which, int n, const float *x, const float *y, float *out, void *stream) {
-  AGX_REQUIRE(which >= AGX_MATH_SIN && which <= AGX_MATH_EXPM1, "which = %d: not an AGX_MATH_* id", which);
+  AGX_REQUIRE(which >= AGX_MATH_SIN && which <= AGX_MATH_TANH, "which = %d: not an AGX_MATH_* id", which);
   AGX_REQUIRE(n >= 0, "n = %d", n);
   AGX_REQUIRE(n == 0 || (x && out && (which != AGX_MATH_ATAN2 || y)), "null buffer");
   if (n == 0) return AGX_OK;

@@ -367,3 +367,338 @@ extern "C" int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_s
                      env_index_base, env_step, noise_out);
   return check_launch("agx_policy_noise");
 }
+
+// ---- recurrent actor: encoder MLP -> GRU cell -> linear head as ONE launch ----------------------------------------------------
+// sample-factory's actor with a recurrent core (sf_inference_class.py:80-101, nn_inference_class.py:77-101).  The mapping of
+// k_policy_act: a workgroup of four waves owns 32 envs, every linear map is layer_tiles.  LDS, in floats per env column:
+//   [buf0 | buf1]  the encoder's ping-pong pair (activation a lives in buffer a & 1; the encoder's output is the cell's input x)
+//   [h]            H: the state of the tile, h' in place after the gates
+//   [gi | gh]      3H each: W_ih x + b_ih and W_hh h + b_hh, gate order r, z, n; afterwards the head's output (<= 128 <= 6H rows)
+// Nothing crosses workgroups: a tile reads its rows of the state buffer before the gates and writes them after.
+namespace {
+constexpr int kMaxEncoderLayers = AGX_POLICY_MAX_LAYERS - 2;
+constexpr int kMaxMaps = kMaxEncoderLayers + 3;  // the encoder's layers, then w_ih, w_hh and the head
+static_assert(kMaxMaps == AGX_POLICY_MAX_LAYERS + 1, "the per-map arrays hold every encoder layer the check admits plus three");
+
+struct RecurrentK {
+  const float *w[kMaxMaps];  // encoder layers 0 .. L-1, then w_ih, w_hh, head: packed [k8][cout]
+  const float *b[kMaxMaps];
+  int k8[kMaxMaps];
+  int cout[kMaxMaps];
+  int num_encoder_layers, in_dim, hidden, num_actions, adaptive, activation;
+  const float *obs, *eps, *logstd, *mean, *denom;
+  const uint8_t *done0, *done1;
+  float *state, *actions, *mu_out, *logstd_out;
+  float clip;
+  int n, flags, env_base, step;
+  int buf1, off_h, off_gi;  // first float of the second ping-pong buffer, of h, of gi (gh follows gi)
+  uint64_t seed;
+};
+
+AGX_DEV void run_layer(const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ x, float *__restrict__ y, int k8,
+                       int cout, int act, int wave, int lane) {
+  const int tiles = cout >> 5;
+  const int nt = wave < tiles ? (tiles - wave + kWaves - 1) / kWaves : 0;  // wave-uniform, <= 4 (the check: cout <= 512)
+  if (nt == 1) layer_tiles<1>(w, bias, x, y, k8, cout, act, wave, lane);
+  else if (nt == 2) layer_tiles<2>(w, bias, x, y, k8, cout, act, wave, lane);
+  else if (nt == 3) layer_tiles<3>(w, bias, x, y, k8, cout, act, wave, lane);
+  else if (nt == 4) layer_tiles<4>(w, bias, x, y, k8, cout, act, wave, lane);
+}
+
+__global__ void __launch_bounds__(64 * kWaves) k_recurrent_act(RecurrentK a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long env0 = (long long)blockIdx.x * kTile;
+  const int live = (int)min((long long)kTile, (long long)a.n - env0);  // envs of this tile, 1 .. 32
+  const int L = a.num_encoder_layers, H = a.hidden;
+  const bool after = (a.flags & AGX_POLICY_RESET_AFTER) != 0;
+  float *__restrict__ hl = lds + a.off_h;
+  // ---- the observations as in k_policy_act, and the state of the tile: [H][32], dead envs and flagged ones (reset before) zero ----
+  {
+    float *__restrict__ x0 = lds;
+    const float *__restrict__ src = a.obs + (size_t)env0 * (size_t)a.in_dim;
+    const int k8 = a.k8[0];
+    for (int i = tid; i < kTile * k8; i += 64 * kWaves) {
+      const int k = i >> 5, col = i & 31;
+      float v = 0.0f;
+      if (col < live && k < a.in_dim) {
+        v = src[(size_t)col * (size_t)a.in_dim + (size_t)k];
+        if (a.mean) {
+          v = (v - a.mean[k]) / a.denom[k];
+          v = (v < -a.clip) ? -a.clip : ((v > a.clip) ? a.clip : v);
+        }
+      }
+      x0[k * kTile + col] = v;
+    }
+    // lanes along the envs, like the observations: LDS words in order.  In memory neighbouring lanes are a row of H floats apart,
+    // so an instruction touches 32 cache lines -- which the following values of j read again out of L2.  The state is
+    // H x 128 bytes per tile against a kernel bound by its matrix chain; the store after the gates mirrors it
+    const float *__restrict__ hs = a.state + (size_t)env0 * (size_t)H;
+    for (int i = tid; i < kTile * H; i += 64 * kWaves) {
+      const int j = i >> 5, col = i & 31;
+      float v = 0.0f;
+      if (col < live) {
+        bool flagged = false;
+        if (!after) flagged = (a.done0 && a.done0[env0 + col]) || (a.done1 && a.done1[env0 + col]);
+        if (!flagged) v = hs[(size_t)col * (size_t)H + (size_t)j];
+      }
+      hl[j * kTile + col] = v;
+    }
+  }
+  __syncthreads();
+  // ---- the encoder: the activation follows every layer ----
+  for (int l = 0; l < L; ++l) {
+    const float *__restrict__ x = lds + ((l & 1) ? a.buf1 : 0);
+    float *__restrict__ y = lds + ((l & 1) ? 0 : a.buf1);
+    run_layer(a.w[l], a.b[l], x, y, a.k8[l], a.cout[l], a.activation, wave, lane);
+    __syncthreads();
+  }
+  // ---- the cell ----
+  const float *__restrict__ xe = lds + ((L & 1) ? a.buf1 : 0);
+  float *__restrict__ gi = lds + a.off_gi;
+  float *__restrict__ gh = gi + 3 * H * kTile;
+  run_layer(a.w[L], a.b[L], xe, gi, a.k8[L], a.cout[L], AGX_POLICY_NONE, wave, lane);
+  run_layer(a.w[L + 1], a.b[L + 1], hl, gh, a.k8[L + 1], a.cout[L + 1], AGX_POLICY_NONE, wave, lane);
+  __syncthreads();
+  {
+    float *__restrict__ hs = a.state + (size_t)env0 * (size_t)H;
+    for (int i = tid; i < kTile * H; i += 64 * kWaves) {
+      const int j = i >> 5, col = i & 31;
+      const float sr = gi[j * kTile + col] + gh[j * kTile + col];
+      const float r = sigmoid_cw(sr);
+      const float sz = gi[(H + j) * kTile + col] + gh[(H + j) * kTile + col];
+      const float z = sigmoid_cw(sz);
+      const float t = r * gh[(2 * H + j) * kTile + col];
+      const float u = gi[(2 * H + j) * kTile + col] + t;
+      const float nn = tanh_cw(u);
+      const float omz = 1.0f - z;
+      const float b = omz * nn;
+      const float c = z * hl[j * kTile + col];
+      const float hn = b + c;
+      hl[j * kTile + col] = hn;  // this thread's own element: in place
+      if (col < live) {
+        bool flagged = false;
+        if (after) flagged = (a.done0 && a.done0[env0 + col]) || (a.done1 && a.done1[env0 + col]);
+        hs[(size_t)col * (size_t)H + (size_t)j] = flagged ? 0.0f : hn;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- the head: H -> P rows padded to 32, written over gi (and into gh: both are dead) ----
+  float *po = gi;
+  run_layer(a.w[L + 2], a.b[L + 2], hl, po, a.k8[L + 2], a.cout[L + 2], AGX_POLICY_NONE, wave, lane);
+  __syncthreads();
+  // ---- mean -> (sample) -> (clamp) -> [N][A] ----
+  const int A = a.num_actions;
+  const size_t out0 = (size_t)env0 * (size_t)A;
+  for (int i = tid; i < live * A; i += 64 * kWaves) {
+    const int col = i / A, j = i - col * A;
+    const float mu = po[j * kTile + col];
+    const bool have_ls = a.adaptive || a.logstd;
+    const float ls = a.adaptive ? po[(A + j) * kTile + col] : (a.logstd ? a.logstd[j] : 0.0f);
+    float v = mu;
+    if (a.flags & AGX_POLICY_SAMPLE) {
+      const float sigma = exp_cw(ls);
+      const float e = a.eps ? a.eps[out0 + i] : policy_normal(a.seed, a.env_base + (int)env0 + col, a.step, j);
+      const float t = e * sigma;
+      v = mu + t;
+    }
+    if (a.flags & AGX_POLICY_CLAMP) v = (v < -1.0f) ? -1.0f : ((v > 1.0f) ? 1.0f : v);
+    a.actions[out0 + i] = v;
+    if (a.mu_out) a.mu_out[out0 + i] = mu;
+    if (a.logstd_out && have_ls) a.logstd_out[out0 + i] = ls;
+  }
+}
+}  // namespace
+
+struct AgxRecurrent {
+  int num_encoder_layers, activation, hidden, num_actions, adaptive;
+  int dims[kMaxEncoderLayers + 1];  // the encoder's widths
+  int k8[kMaxMaps], cout[kMaxMaps];
+  float *w[kMaxMaps], *b[kMaxMaps];  // encoder, w_ih, w_hh, head
+  float *mean, *denom, *logstd;
+  bool has_norm, has_logstd;
+  float clip;
+  int buf1, off_h, off_gi;
+  size_t lds_bytes;
+};
+
+extern "C" int agx_recurrent_destroy(AgxRecurrent *p) {
+  if (!p) return AGX_OK;
+  for (int l = 0; l < kMaxMaps; ++l) {
+    if (p->w[l]) (void)hipFree(p->w[l]);
+    if (p->b[l]) (void)hipFree(p->b[l]);
+  }
+  if (p->mean) (void)hipFree(p->mean);
+  if (p->denom) (void)hipFree(p->denom);
+  if (p->logstd) (void)hipFree(p->logstd);
+  delete p;
+  return AGX_OK;
+}
+
+namespace {
+// floats per env column of the encoder's two ping-pong buffers: activation a (0 = the input .. L = the cell's input) in buffer a & 1
+void recurrent_widths(int L, const int32_t *dims, int width[2]) {
+  width[0] = width[1] = 0;
+  for (int a = 0; a <= L; ++a) {
+    const int wa = a == 0 ? round_up(dims[0], 8) : dims[a];
+    if (wa > width[a & 1]) width[a & 1] = wa;
+  }
+}
+}  // namespace
+
+extern "C" int agx_recurrent_check(int num_encoder_layers, const int32_t *dims, int hidden, int head_out, size_t *lds_bytes) {
+  const int L = num_encoder_layers;
+  AGX_REQUIRE(dims, "agx_recurrent_create: null dims");
+  AGX_REQUIRE(L >= 1 && L <= kMaxEncoderLayers, "agx_recurrent_create: num_encoder_layers = %d, supported: 1 .. %d", L, kMaxEncoderLayers);
+  AGX_REQUIRE(dims[0] >= 1 && dims[0] <= AGX_POLICY_MAX_WIDTH, "agx_recurrent_create: input width %d, supported: 1 .. %d", dims[0],
+              AGX_POLICY_MAX_WIDTH);
+  for (int l = 1; l <= L; ++l)
+    AGX_REQUIRE(dims[l] >= 32 && dims[l] <= AGX_POLICY_MAX_WIDTH && dims[l] % 32 == 0,
+                "agx_recurrent_create: encoder width %d (output of layer %d): a multiple of 32 up to %d is supported", dims[l], l - 1,
+                AGX_POLICY_MAX_WIDTH);
+  AGX_REQUIRE(hidden >= 32 && hidden <= AGX_POLICY_MAX_WIDTH && hidden % 32 == 0,
+              "agx_recurrent_create: hidden size %d: a multiple of 32 within 32 .. %d is supported", hidden, AGX_POLICY_MAX_WIDTH);
+  AGX_REQUIRE(head_out >= 1 && head_out <= 128, "agx_recurrent_create: head width %d, supported: 1 .. 128 (64 actions, means and log-std)",
+              head_out);
+  int width[2];
+  recurrent_widths(L, dims, width);
+  // x (the ping-pong pair), h, gi and gh are live together in the cell
+  const size_t bytes = (size_t)(width[0] + width[1] + 7 * hidden) * kTile * sizeof(float);
+  AGX_REQUIRE(bytes <= kLdsLimit,
+              "agx_recurrent_create: encoder activations of widths %d + %d and the cell's 7 x %d (h, gi, gh) for 32 envs need %zu bytes of "
+              "LDS, a workgroup has %zu", width[0], width[1], hidden, bytes, kLdsLimit);
+  // 3 x hidden channels are at most sixteen tiles of 32, four per wave: implied by the LDS limit (7 x 192 x 128 bytes exceed it)
+  AGX_REQUIRE(3 * hidden <= 32 * 4 * kWaves, "agx_recurrent_create: hidden size %d: 3 x hidden exceeds %d gate channels", hidden, 32 * 4 * kWaves);
+  if (lds_bytes) *lds_bytes = bytes;
+  return AGX_OK;
+}
+
+extern "C" int agx_recurrent_create(int num_encoder_layers, const int32_t *dims, int hidden, int num_actions, int adaptive_stddev,
+                                    const float *const *enc_weights, const float *const *enc_biases, const float *w_ih, const float *w_hh,
+                                    const float *b_ih, const float *b_hh, const float *head_weight, const float *head_bias,
+                                    int hidden_activation, AgxRecurrent **out) {
+  AGX_REQUIRE(out, "agx_recurrent_create: null handle pointer");
+  *out = nullptr;
+  AGX_REQUIRE(dims && enc_weights && enc_biases && w_ih && w_hh && b_ih && b_hh && head_weight && head_bias, "agx_recurrent_create: null argument");
+  AGX_REQUIRE(num_actions >= 1 && num_actions <= 64, "agx_recurrent_create: num_actions = %d, supported: 1 .. 64", num_actions);
+  const int L = num_encoder_layers, H = hidden, P = adaptive_stddev ? 2 * num_actions : num_actions;
+  size_t lds_bytes = 0;
+  if (int e = agx_recurrent_check(L, dims, H, P, &lds_bytes)) return e;
+  AGX_REQUIRE(hidden_activation == AGX_POLICY_ELU || hidden_activation == AGX_POLICY_RELU,
+              "agx_recurrent_create: hidden_activation = %d (AGX_POLICY_ELU or _RELU)", hidden_activation);
+  for (int l = 0; l < L; ++l) AGX_REQUIRE(enc_weights[l] && enc_biases[l], "agx_recurrent_create: encoder layer %d: null weight or bias", l);
+  AgxRecurrent *p = new AgxRecurrent();
+  p->num_encoder_layers = L; p->activation = hidden_activation; p->hidden = H; p->num_actions = num_actions; p->adaptive = adaptive_stddev ? 1 : 0;
+  for (int l = 0; l <= L; ++l) p->dims[l] = dims[l];
+  for (int l = 0; l < kMaxMaps; ++l) { p->w[l] = p->b[l] = nullptr; p->k8[l] = p->cout[l] = 0; }
+  p->mean = p->denom = p->logstd = nullptr;
+  p->has_norm = p->has_logstd = false;
+  p->clip = 0.0f;
+  p->lds_bytes = lds_bytes;
+  int width[2];
+  recurrent_widths(L, dims, width);
+  p->buf1 = width[0] * kTile;
+  p->off_h = (width[0] + width[1]) * kTile;
+  p->off_gi = p->off_h + H * kTile;
+  hipError_t e = hipSuccess;
+  static_assert(kMaxEncoderLayers + 3 <= kMaxMaps, "map L + 2 (the head) is the last entry");
+  for (int l = 0; l < L + 3 && e == hipSuccess; ++l) {
+    // rows, columns and the host arrays of map l: the encoder's layers, W_ih [3H][I], W_hh [3H][H], the head [P][H]
+    const int k = l < L ? dims[l] : (l == L ? dims[L] : H);
+    const int co = l < L ? dims[l + 1] : (l < L + 2 ? 3 * H : P);
+    const float *wsrc = l < L ? enc_weights[l] : (l == L ? w_ih : (l == L + 1 ? w_hh : head_weight));
+    const float *bsrc = l < L ? enc_biases[l] : (l == L ? b_ih : (l == L + 1 ? b_hh : head_bias));
+    const int cop = round_up(co, 32);  // only the head is padded: zero weights and zero biases the caller never sees
+    p->k8[l] = round_up(k, 8);
+    p->cout[l] = cop;
+    std::vector<float> padded((size_t)cop * k, 0.0f), bias((size_t)cop, 0.0f);
+    for (size_t i = 0; i < (size_t)co * k; ++i) padded[i] = wsrc[i];
+    for (int i = 0; i < co; ++i) bias[i] = bsrc[i];
+    std::vector<float> packed(agx_vae_packed_floats(cop, k));
+    agx_vae_pack_weight(cop, k, padded.data(), packed.data());
+    e = hipMalloc((void **)&p->w[l], packed.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&p->b[l], bias.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc((void **)&p->mean, (size_t)dims[0] * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&p->denom, (size_t)dims[0] * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&p->logstd, (size_t)num_actions * sizeof(float));
+  // above 64 KiB of dynamic LDS the runtime may want to be told.  The attribute belongs to the kernel, not to this actor: always
+  // the limit the check admits, so that a smaller actor created later does not lower it under an earlier one
+  if (e == hipSuccess) {
+    (void)hipFuncSetAttribute((const void *)k_recurrent_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
+    (void)hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    agx_recurrent_destroy(p);
+    (void)hipGetLastError();
+    return fail(AGX_E_LAUNCH, "agx_recurrent_create: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return AGX_OK;
+}
+
+extern "C" int agx_recurrent_set_input_norm(AgxRecurrent *p, const float *mean, const float *denom, float clip) {
+  AGX_REQUIRE(p, "agx_recurrent_set_input_norm: null handle");
+  if (!mean && !denom) { p->has_norm = false; return AGX_OK; }
+  AGX_REQUIRE(mean && denom, "agx_recurrent_set_input_norm: mean and denom come together");
+  AGX_REQUIRE(clip > 0.0f, "agx_recurrent_set_input_norm: clip = %g must be positive", (double)clip);
+  hipError_t e = hipMemcpy(p->mean, mean, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->denom, denom, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_recurrent_set_input_norm: %s", hipGetErrorString(e));
+  p->clip = clip;
+  p->has_norm = true;
+  return AGX_OK;
+}
+
+extern "C" int agx_recurrent_set_logstd(AgxRecurrent *p, const float *logstd) {
+  AGX_REQUIRE(p, "agx_recurrent_set_logstd: null handle");
+  AGX_REQUIRE(!p->adaptive, "agx_recurrent_set_logstd: the head is adaptive: it emits the log-std itself");
+  if (!logstd) { p->has_logstd = false; return AGX_OK; }
+  hipError_t e = hipMemcpy(p->logstd, logstd, (size_t)p->num_actions * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_recurrent_set_logstd: %s", hipGetErrorString(e));
+  p->has_logstd = true;
+  return AGX_OK;
+}
+
+extern "C" int agx_recurrent_act(AgxRecurrent *p, int num_envs, const float *obs, float *hidden, const uint8_t *done0, const uint8_t *done1,
+                                 float *actions, float *mu_out, float *logstd_out, const float *eps, int flags, uint64_t rng_seed,
+                                 int env_index_base, int env_step, void *stream) {
+  AGX_REQUIRE(p, "agx_recurrent_act: null handle");
+  AGX_REQUIRE(num_envs >= 0 && num_envs <= (1 << 22), "agx_recurrent_act: num_envs = %d, supported: 0 .. %d", num_envs, 1 << 22);
+  AGX_REQUIRE((flags & ~(AGX_POLICY_SAMPLE | AGX_POLICY_CLAMP | AGX_POLICY_RESET_AFTER)) == 0, "agx_recurrent_act: flags = %d", flags);
+  const bool have_logstd = p->adaptive || p->has_logstd;
+  AGX_REQUIRE(!(flags & AGX_POLICY_SAMPLE) || have_logstd,
+              "agx_recurrent_act: AGX_POLICY_SAMPLE needs a logstd (an adaptive head or agx_recurrent_set_logstd)");
+  AGX_REQUIRE(!logstd_out || have_logstd, "agx_recurrent_act: logstd_out needs a logstd (an adaptive head or agx_recurrent_set_logstd)");
+  if (num_envs == 0) return AGX_OK;
+  AGX_REQUIRE(obs, "agx_recurrent_act: null obs");
+  AGX_REQUIRE(hidden, "agx_recurrent_act: null hidden");
+  AGX_REQUIRE(actions, "agx_recurrent_act: null actions");
+  RecurrentK a;
+  for (int l = 0; l < kMaxMaps; ++l) { a.w[l] = p->w[l]; a.b[l] = p->b[l]; a.k8[l] = p->k8[l]; a.cout[l] = p->cout[l]; }
+  a.num_encoder_layers = p->num_encoder_layers; a.in_dim = p->dims[0]; a.hidden = p->hidden; a.num_actions = p->num_actions;
+  a.adaptive = p->adaptive; a.activation = p->activation;
+  a.obs = obs; a.eps = eps; a.logstd = p->has_logstd ? p->logstd : nullptr;
+  a.mean = p->has_norm ? p->mean : nullptr; a.denom = p->has_norm ? p->denom : nullptr;
+  a.done0 = done0; a.done1 = done1;
+  a.state = hidden; a.actions = actions; a.mu_out = mu_out; a.logstd_out = logstd_out;
+  a.clip = p->clip;
+  a.n = num_envs; a.flags = flags; a.env_base = env_index_base; a.step = env_step;
+  a.buf1 = p->buf1; a.off_h = p->off_h; a.off_gi = p->off_gi;
+  a.seed = rng_seed;
+  hipLaunchKernelGGL(k_recurrent_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->lds_bytes, (hipStream_t)stream, a);
+  return check_launch("agx_recurrent_act");
+}
+
+extern "C" int agx_recurrent_noise(const AgxRecurrent *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                                   void *stream) {
+  AGX_REQUIRE(p && noise_out, "agx_recurrent_noise: null argument");
+  AGX_REQUIRE(num_envs > 0 && num_envs <= (1 << 22), "agx_recurrent_noise: num_envs = %d, supported: 1 .. %d", num_envs, 1 << 22);
+  const long long total = (long long)num_envs * p->num_actions;
+  hipLaunchKernelGGL(k_policy_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, p->num_actions, rng_seed,
+                     env_index_base, env_step, noise_out);
+  return check_launch("agx_recurrent_noise");
+}

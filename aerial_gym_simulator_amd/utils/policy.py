@@ -253,3 +253,410 @@ class ActorMLP:
         _lib.check(self._lib.agx_policy_noise(self._handle, n, self.rng_seed, self.env_index_base, int(step) & 0x7FFFFFFF, _lib.dptr(out),
                                               _lib.current_stream(self.device)), "agx_policy_noise")
         return out
+
+
+# ---- recurrent actors: sample-factory's encoder MLP -> GRU -> linear head --------------------------------------------------------
+SF_NORM_EPSILON = 1e-5  # sample-factory RunningMeanStdInPlace: (x - mean) / sqrt(var + eps) ...
+SF_NORM_CLIP = 5.0      # ... clamped to +-5 (its published defaults: epsilon=1e-5, clip=5.0)
+_SF_IGNORED_PREFIXES = ("critic_linear.", "returns_normalizer.")
+_SF_NORM = r"obs_normalizer\.running_mean_std\.running_mean_std\.([^.]+)\.(running_mean|running_var|count)"
+_SF_ENC = r"encoder\.encoders\.([^.]+)\.mlp_head\.(\d+)\.(weight|bias)"
+_SF_CORE = ("core.core.weight_ih_l0", "core.core.weight_hh_l0", "core.core.bias_ih_l0", "core.core.bias_hh_l0")
+_SF_HEAD = ("action_parameterization.distribution_linear.weight", "action_parameterization.distribution_linear.bias")
+_SF_STDDEV = "action_parameterization.learned_stddev"
+
+
+def check_recurrent_dims(dims, hidden, head_out):
+    """the limits of agx_recurrent_create for encoder widths [in, ..., cell input], the hidden size and the head's width
+    (ValueError names the offending number); returns the bytes of LDS a workgroup uses.  Host only."""
+    dims = [int(d) for d in dims]
+    lds = C.c_size_t(0)
+    lib = _lib.load()
+    if lib.agx_recurrent_check(len(dims) - 1, (C.c_int32 * len(dims))(*dims), int(hidden), int(head_out), C.byref(lds)) != 0:
+        raise ValueError(lib.agx_last_error().decode("utf-8", "replace"))
+    return int(lds.value)
+
+
+def _f32(t):
+    return np.ascontiguousarray(torch.as_tensor(t).detach().to("cpu", torch.float32).contiguous().numpy())
+
+
+def recurrent_arrays_from_state_dict(sd):
+    """the arrays of a sample-factory actor-critic state dict (`torch.load(path)["model"]`) with one observation key, an MLP
+    encoder, a one-layer GRU core and a linear action head: a dict with obs_key, enc_weights, enc_biases, w_ih, w_hh, b_ih, b_hh,
+    head_weight, head_bias, logstd (None when the head is adaptive) and input_norm (None or (mean, denom, clip)).  ValueError /
+    KeyError name the key that does not fit."""
+    enc, norm, obs_keys = {}, {}, set()
+    for key in sd:
+        k = str(key)
+        m = re.fullmatch(_SF_ENC, k)
+        if m:
+            obs_keys.add(m.group(1))
+            enc.setdefault(int(m.group(2)), {})[m.group(3)] = key
+            continue
+        m = re.fullmatch(_SF_NORM, k)
+        if m:
+            obs_keys.add(m.group(1))
+            norm[m.group(2)] = key
+            continue
+        if k in _SF_CORE or k in _SF_HEAD or k == _SF_STDDEV or k.startswith(_SF_IGNORED_PREFIXES) or k.endswith(".count"):
+            continue
+        if re.fullmatch(r"core\.core\.(weight|bias)_(ih|hh)_l[1-9]\d*(_reverse)?", k) or k.endswith("_reverse"):
+            raise ValueError(f"sample-factory checkpoint: key {k!r}: only a one-layer, one-direction core is supported")
+        raise ValueError(f"sample-factory checkpoint: key {k!r} is not part of an actor with one MLP encoder, one GRU layer and a linear "
+                         "action head (decoder layers, conv encoders, separate actor_encoder / critic_encoder and LSTM cores are not supported)")
+    if len(obs_keys) != 1:
+        raise ValueError(f"sample-factory checkpoint: observation keys {sorted(obs_keys)}: exactly one is supported")
+    obs_key = next(iter(obs_keys))
+    if not enc:
+        raise KeyError(f"sample-factory checkpoint has no 'encoder.encoders.{obs_key}.mlp_head.0.weight'")
+    for idx in sorted(enc):
+        if idx % 2 != 0:
+            raise ValueError(f"sample-factory checkpoint: 'encoder.encoders.{obs_key}.mlp_head.{idx}' holds parameters; Linear layers sit at "
+                             "the even indices")
+    out = {"obs_key": obs_key, "enc_weights": [], "enc_biases": []}
+    for i in range(len(enc)):
+        for kind, dst in (("weight", out["enc_weights"]), ("bias", out["enc_biases"])):
+            key = f"encoder.encoders.{obs_key}.mlp_head.{2 * i}.{kind}"
+            if key not in sd:
+                raise KeyError(f"sample-factory checkpoint has no {key!r} (layers found: {sorted(enc)})")
+            dst.append(_f32(sd[key]))
+    for key in _SF_CORE + _SF_HEAD:
+        if key not in sd:
+            raise KeyError(f"sample-factory checkpoint has no {key!r}")
+    w_ih, w_hh, b_ih, b_hh = (_f32(sd[k]) for k in _SF_CORE)
+    hidden = w_hh.shape[1]
+    for name, arr, want in (("core.core.weight_ih_l0", w_ih, (3 * hidden, out["enc_weights"][-1].shape[0])),
+                            ("core.core.weight_hh_l0", w_hh, (3 * hidden, hidden)), ("core.core.bias_ih_l0", b_ih, (3 * hidden,)),
+                            ("core.core.bias_hh_l0", b_hh, (3 * hidden,))):
+        if arr.shape != want:
+            kind = " (4 x hidden rows: an LSTM)" if arr.shape[0] == 4 * hidden else ""
+            raise ValueError(f"sample-factory checkpoint: {name!r} has shape {arr.shape}{kind}; a GRU of hidden size {hidden} has {want}")
+    out.update(w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh, head_weight=_f32(sd[_SF_HEAD[0]]), head_bias=_f32(sd[_SF_HEAD[1]]))
+    out["logstd"] = _f32(sd[_SF_STDDEV]).reshape(-1) if _SF_STDDEV in sd else None
+    out["input_norm"] = None
+    if "running_mean" in norm or "running_var" in norm:
+        for kind in ("running_mean", "running_var"):
+            if kind not in norm:
+                raise KeyError(f"sample-factory checkpoint has no 'obs_normalizer.running_mean_std.running_mean_std.{obs_key}.{kind}' next to "
+                               "the other half of the normaliser")
+        mean, var = _f32(sd[norm["running_mean"]]), _f32(sd[norm["running_var"]])  # float64 in the file: rounded to float32 first
+        out["input_norm"] = (mean, np.sqrt(var + np.float32(SF_NORM_EPSILON), dtype=np.float32), SF_NORM_CLIP)
+    return out
+
+
+def _check_sf_config(cfg, where):
+    """the entries of a sample-factory config.json this actor depends on (ValueError names the entry); returns normalize_input"""
+    want = (("rnn_type", lambda v: v == "gru", "'gru'"), ("rnn_num_layers", lambda v: v == 1, "1"),
+            ("nonlinearity", lambda v: v in ("elu", "relu"), "'elu' or 'relu'"), ("decoder_mlp_layers", lambda v: list(v) == [], "[]"),
+            ("continuous_tanh_scale", lambda v: float(v) == 0.0, "0"), ("obs_subtract_mean", lambda v: float(v) == 0.0, "0"),
+            ("obs_scale", lambda v: float(v) == 1.0, "1"))
+    for name, ok, text in want:
+        if name in cfg and not ok(cfg[name]):
+            raise ValueError(f"{where}: {name} = {cfg[name]!r}; supported: {text}")
+    return bool(cfg.get("normalize_input", True))
+
+
+def find_sample_factory_checkpoint(path_or_dir, kind="best"):
+    """a .pth file as it is; of a checkpoint_p0 directory the newest best_* (kind 'best') or checkpoint_* (kind 'latest')"""
+    import glob
+    import os
+
+    path = str(path_or_dir)
+    if os.path.isfile(path):
+        return path
+    if kind not in ("best", "latest"):
+        raise ValueError(f"load_checkpoint_kind {kind!r}; supported: 'best', 'latest'")
+    prefix = {"best": "best", "latest": "checkpoint"}[kind]
+    found = sorted(glob.glob(os.path.join(path, f"{prefix}_*")))  # zero-padded train step in the name: sorted = oldest first
+    if not found:
+        raise FileNotFoundError(f"{path}: no {prefix}_* checkpoint")
+    return found[-1]
+
+
+class RecurrentActor:
+    """actor(obs, done) -> actions [N, A] of an encoder MLP -> GRU cell -> linear head; the state lives in `actor.hidden` [N, H].
+    Build with from_arrays or from_sample_factory_checkpoint."""
+
+    def __init__(self, enc_weights, enc_biases, w_ih, w_hh, b_ih, b_hh, head_weight, head_bias, logstd=None, activation="elu", input_norm=None,
+                 device="cuda:0", task=None, rng_seed=None, env_index_base=None):
+        if activation not in ("elu", "relu"):
+            raise ValueError(f"RecurrentActor: activation {activation!r}; supported: 'elu', 'relu'")
+        self.activation = activation
+        arr = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))  # noqa: E731
+        self.enc_weights, self.enc_biases = [arr(w) for w in enc_weights], [arr(b) for b in enc_biases]
+        if len(self.enc_weights) != len(self.enc_biases) or not self.enc_weights:
+            raise ValueError(f"RecurrentActor: {len(self.enc_weights)} encoder weights and {len(self.enc_biases)} biases")
+        for l, (w, b) in enumerate(zip(self.enc_weights, self.enc_biases)):
+            if w.ndim != 2 or b.shape != (w.shape[0],):
+                raise ValueError(f"RecurrentActor: encoder layer {l}: weight {w.shape} and bias {b.shape} are not [out, in] and [out]")
+            if l and w.shape[1] != self.enc_weights[l - 1].shape[0]:
+                raise ValueError(f"RecurrentActor: encoder layer {l} reads {w.shape[1]} inputs, layer {l - 1} writes {self.enc_weights[l - 1].shape[0]}")
+        self.dims = [self.enc_weights[0].shape[1]] + [w.shape[0] for w in self.enc_weights]
+        self.w_ih, self.w_hh, self.b_ih, self.b_hh = arr(w_ih), arr(w_hh), arr(b_ih).reshape(-1), arr(b_hh).reshape(-1)
+        self.head_weight, self.head_bias = arr(head_weight), arr(head_bias).reshape(-1)
+        if self.w_hh.ndim != 2 or self.w_hh.shape[0] != 3 * self.w_hh.shape[1]:
+            raise ValueError(f"RecurrentActor: w_hh {self.w_hh.shape} is not [3 H, H] (a GRU, gates r, z, n)")
+        self.hidden_dim = H = self.w_hh.shape[1]
+        if self.w_ih.shape != (3 * H, self.dims[-1]) or self.b_ih.shape != (3 * H,) or self.b_hh.shape != (3 * H,):
+            raise ValueError(f"RecurrentActor: w_ih {self.w_ih.shape}, b_ih {self.b_ih.shape}, b_hh {self.b_hh.shape} do not fit a GRU of "
+                             f"{self.dims[-1]} inputs and hidden size {H}")
+        if self.head_weight.ndim != 2 or self.head_weight.shape[1] != H or self.head_bias.shape != (self.head_weight.shape[0],):
+            raise ValueError(f"RecurrentActor: head weight {self.head_weight.shape} and bias {self.head_bias.shape} do not read {H} inputs")
+        P = self.head_weight.shape[0]
+        self.logstd = None if logstd is None else arr(logstd).reshape(-1)
+        self.adaptive = self.logstd is None
+        if self.adaptive and P % 2:
+            raise ValueError(f"RecurrentActor: an adaptive head emits means and log-std: {P} outputs is odd (pass logstd= for a constant one)")
+        self.action_dim = P // 2 if self.adaptive else P
+        if not self.adaptive and self.logstd.shape != (self.action_dim,):
+            raise ValueError(f"RecurrentActor: logstd has {self.logstd.size} entries, the head has {self.action_dim} actions")
+        if not 1 <= self.action_dim <= 64:
+            raise ValueError(f"RecurrentActor: {self.action_dim} actions; supported: 1 .. 64")
+        self.obs_dim = self.dims[0]
+        self.lds_bytes = check_recurrent_dims(self.dims, H, P)
+        self.input_norm = None
+        if input_norm is not None:
+            mean, denom, clip = input_norm
+            mean, denom = arr(mean).reshape(-1), arr(denom).reshape(-1)
+            if mean.shape != (self.obs_dim,) or denom.shape != (self.obs_dim,):
+                raise ValueError(f"RecurrentActor: input_norm of widths {mean.size} / {denom.size}, the net reads {self.obs_dim} inputs")
+            self.input_norm = (mean, denom, float(clip))
+        self.device = str(device)
+        self.task = task
+        env = getattr(task, "sim_env", None)
+        self.rng_seed = int(rng_seed if rng_seed is not None else getattr(env, "rng_seed", 0)) & 0xFFFFFFFFFFFFFFFF
+        self.env_index_base = int(env_index_base if env_index_base is not None else getattr(env, "env_offset", 0))
+        self.step = 0
+        self.hidden = None  # [N, H], allocated by the first call
+        self.mean = self.logstd_out = None
+        self._may_resize = True
+        self._out = {}
+        self._handle = None
+        self._is_cpu = torch.device(self.device).type == "cpu"
+        if self._is_cpu:
+            t = torch.from_numpy
+            self._cpu = {"enc": [(t(w), t(b)) for w, b in zip(self.enc_weights, self.enc_biases)], "ih": (t(self.w_ih), t(self.b_ih)),
+                         "hh": (t(self.w_hh), t(self.b_hh)), "head": (t(self.head_weight), t(self.head_bias))}
+        else:
+            self._lib = _lib.load()
+            n = len(self.enc_weights)
+            wp = (C.c_void_p * n)(*[w.ctypes.data for w in self.enc_weights])
+            bp = (C.c_void_p * n)(*[b.ctypes.data for b in self.enc_biases])
+            handle = C.c_void_p()
+            with torch.cuda.device(torch.device(self.device)):
+                _lib.check(self._lib.agx_recurrent_create(n, (C.c_int32 * len(self.dims))(*self.dims), H, self.action_dim, int(self.adaptive), wp, bp,
+                                                          self.w_ih.ctypes.data, self.w_hh.ctypes.data, self.b_ih.ctypes.data, self.b_hh.ctypes.data,
+                                                          self.head_weight.ctypes.data, self.head_bias.ctypes.data, ACTIVATIONS[activation],
+                                                          C.byref(handle)), "agx_recurrent_create")
+                self._handle = handle
+                if self.input_norm is not None:
+                    mean, denom, clip = self.input_norm
+                    _lib.check(self._lib.agx_recurrent_set_input_norm(handle, mean.ctypes.data, denom.ctypes.data, clip), "agx_recurrent_set_input_norm")
+                if not self.adaptive:
+                    _lib.check(self._lib.agx_recurrent_set_logstd(handle, self.logstd.ctypes.data), "agx_recurrent_set_logstd")
+
+    def __del__(self):
+        handle, self._handle = getattr(self, "_handle", None), None
+        if handle:
+            self._lib.agx_recurrent_destroy(handle)
+
+    # ---- constructors ----------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, enc_weights, enc_biases, w_ih, w_hh, b_ih, b_hh, head_weight, head_bias, logstd=None, activation="elu",
+                    input_norm=None, device="cuda:0", **kw):
+        return cls(enc_weights, enc_biases, w_ih, w_hh, b_ih, b_hh, head_weight, head_bias, logstd=logstd, activation=activation,
+                   input_norm=input_norm, device=device, **kw)
+
+    @classmethod
+    def from_sample_factory_checkpoint(cls, path_or_dir, device="cuda:0", kind="best", **kw):
+        """a .pth file of sample-factory, or its checkpoint_p0 directory (the newest best_* / checkpoint_* by `kind`).  A
+        config.json beside checkpoint_p0 is read only to validate what this actor depends on and for the nonlinearity."""
+        import json
+        import os
+
+        path = find_sample_factory_checkpoint(path_or_dir, kind)
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+        if not isinstance(ck, dict) or "model" not in ck:
+            raise KeyError(f"{path}: not a sample-factory checkpoint (no 'model' entry)")
+        a = recurrent_arrays_from_state_dict(ck["model"])
+        config = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "config.json")
+        activation, normalize = kw.pop("activation", None), True
+        if os.path.isfile(config):
+            with open(config) as f:
+                cfg = json.load(f)
+            normalize = _check_sf_config(cfg, config)
+            activation = activation or cfg.get("nonlinearity")
+        actor = cls(a["enc_weights"], a["enc_biases"], a["w_ih"], a["w_hh"], a["b_ih"], a["b_hh"], a["head_weight"], a["head_bias"],
+                    logstd=a["logstd"], activation=activation or "elu", input_norm=a["input_norm"] if normalize else None, device=device, **kw)
+        actor.obs_key = a["obs_key"]
+        return actor
+
+    def to(self, device):
+        """the same net on another device (a new handle and a fresh state there); self when it already lives on it"""
+        if torch.device(device) == torch.device(self.device):
+            return self
+        return RecurrentActor(self.enc_weights, self.enc_biases, self.w_ih, self.w_hh, self.b_ih, self.b_hh, self.head_weight, self.head_bias,
+                              logstd=self.logstd, activation=self.activation, input_norm=self.input_norm, device=device, task=self.task,
+                              rng_seed=self.rng_seed, env_index_base=self.env_index_base)
+
+    # ---- the state -------------------------------------------------------------------------------------------------------
+    def allocate(self, n):
+        """a zero state for n envs (what the first call does)"""
+        self.hidden = torch.zeros((int(n), self.hidden_dim), dtype=torch.float32, device=self.device)
+        self._may_resize = False
+        return self.hidden
+
+    def reset(self, env_ids=None):
+        """zero the state rows `env_ids`; without ids all of them, and the next call may come with another batch size"""
+        if env_ids is None:
+            self._may_resize = True
+            if self.hidden is not None:
+                self.hidden.zero_()
+        elif self.hidden is not None:
+            self.hidden[env_ids] = 0.0
+
+    # ---- the call --------------------------------------------------------------------------------------------------------
+    def _buffers(self, n):
+        bufs = self._out.get(n)
+        if bufs is None:
+            bufs = self._out[n] = tuple(torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device) for _ in range(3))
+        return bufs
+
+    _env_step = ActorMLP._env_step
+
+    def __call__(self, obs, done=None, reset="before", out=None, sample=False, clamp=False, eps=None, step=None):
+        """obs [N, obs_dim] float32 -> actions [N, action_dim]; `actor.hidden` advances in place, `actor.mean` and
+        `actor.logstd_out` then hold this call's values.  done: None, one bool / uint8 tensor [N] or a tuple of two (an env with
+        either set is reset) -- `(task.terminations, task.truncations)` goes straight in.  reset "before": a flagged env is
+        evaluated from a zero state (sample-factory's sampler, with the flags of the step that produced obs); "after": it is
+        evaluated with the state it has, and zero is stored (the reference's dce_nn_navigation.py).  sample / clamp / eps / step
+        / out as for ActorMLP; sigma = exp(logstd) of the head."""
+        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype is not torch.float32:
+            raise ValueError(f"RecurrentActor: observations must be float32 [N, {self.obs_dim}], got {obs.dtype} {tuple(obs.shape)}")
+        if reset not in ("before", "after"):
+            raise ValueError(f"RecurrentActor: reset {reset!r}; supported: 'before', 'after'")
+        n = obs.shape[0]
+        if eps is not None and (tuple(eps.shape) != (n, self.action_dim) or eps.dtype is not torch.float32):
+            raise ValueError(f"RecurrentActor: eps must be float32 [{n}, {self.action_dim}]")
+        if sample and eps is None and self._is_cpu:  # refused before the step count or the state moves
+            raise ValueError("RecurrentActor on a CPU device has no generator: pass eps= to sample")
+        flags = () if done is None else (tuple(done) if isinstance(done, (tuple, list)) else (done,))
+        if len(flags) > 2:
+            raise ValueError(f"RecurrentActor: done holds {len(flags)} tensors; one or two are supported")
+        for f in flags:
+            if tuple(f.shape) != (n,) or f.dtype not in (torch.bool, torch.uint8) or not f.is_contiguous():
+                raise ValueError(f"RecurrentActor: a done tensor must be contiguous bool or uint8 [{n}], got {f.dtype} {tuple(f.shape)}")
+        if self.hidden is None or (self.hidden.shape[0] != n and self._may_resize):
+            self.allocate(n)
+        elif self.hidden.shape[0] != n:
+            raise ValueError(f"RecurrentActor: {n} envs, the state holds {self.hidden.shape[0]}: call reset() before changing the batch size")
+        self._may_resize = False
+        buf, mean, logstd_out = self._buffers(n)
+        if out is None:
+            out = buf
+        elif tuple(out.shape) != (n, self.action_dim) or out.dtype is not torch.float32:
+            raise ValueError(f"RecurrentActor: out must be float32 [{n}, {self.action_dim}]")
+        env_step = self._env_step(step, sample and eps is None)
+        if self._is_cpu:
+            return self._call_cpu(obs, flags, reset, out, mean, logstd_out, sample, clamp, eps)
+        if not obs.is_contiguous():
+            obs = obs.contiguous()
+        bits = (_lib.POLICY_SAMPLE if sample else 0) | (_lib.POLICY_CLAMP if clamp else 0) | (_lib.POLICY_RESET_AFTER if reset == "after" else 0)
+        p = _lib.dptr
+        _lib.check(self._lib.agx_recurrent_act(self._handle, n, p(obs), p(self.hidden), p(flags[0]) if flags else None,
+                                               p(flags[1]) if len(flags) > 1 else None, p(out), p(mean), p(logstd_out), p(eps) if sample else None,
+                                               bits, self.rng_seed, self.env_index_base, env_step & 0x7FFFFFFF, _lib.current_stream(self.device)),
+                   "agx_recurrent_act")
+        self.mean, self.logstd_out = mean, logstd_out
+        return out
+
+    def _call_cpu(self, obs, flags, reset, out, mean, logstd_out, sample, clamp, eps):
+        F = torch.nn.functional
+        x = obs
+        if self.input_norm is not None:
+            m, d, clip = self.input_norm
+            x = torch.clamp((x - torch.from_numpy(m)) / torch.from_numpy(d), -clip, clip)
+        for w, b in self._cpu["enc"]:
+            x = F.linear(x, w, b)
+            x = F.elu(x) if self.activation == "elu" else torch.relu(x)
+        flagged = None
+        for f in flags:
+            flagged = (f != 0) if flagged is None else (flagged | (f != 0))
+        h = self.hidden
+        if flagged is not None and reset == "before":
+            h = torch.where(flagged[:, None], torch.zeros_like(h), h)
+        H = self.hidden_dim
+        gi, gh = F.linear(x, *self._cpu["ih"]), F.linear(h, *self._cpu["hh"])
+        r = torch.sigmoid(gi[:, :H] + gh[:, :H])
+        z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        c = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        hn = (1.0 - z) * c + z * h
+        self.hidden.copy_(torch.where(flagged[:, None], torch.zeros_like(hn), hn) if flagged is not None and reset == "after" else hn)
+        y = F.linear(hn, *self._cpu["head"])
+        A = self.action_dim
+        mean.copy_(y[:, :A])
+        logstd_out.copy_(y[:, A:] if self.adaptive else torch.from_numpy(self.logstd).expand_as(mean))
+        a = mean
+        if sample:
+            a = mean + eps * torch.exp(logstd_out)
+        if clamp:
+            a = a.clamp(-1.0, 1.0)
+        out.copy_(a)
+        self.mean, self.logstd_out = mean, logstd_out
+        return out
+
+    def noise(self, n, step):
+        """[n, action_dim]: the normals a sampled call without eps draws at env step `step` (the stream of ActorMLP.noise)"""
+        if self._is_cpu:
+            raise RuntimeError("RecurrentActor.noise: the generator lives in the HIP library; this actor is on a CPU device")
+        out = torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.agx_recurrent_noise(self._handle, n, self.rng_seed, self.env_index_base, int(step) & 0x7FFFFFFF, _lib.dptr(out),
+                                                 _lib.current_stream(self.device)), "agx_recurrent_noise")
+        return out
+
+
+class SampleFactoryInference:
+    """The surface of the reference's two inference classes around RecurrentActor (sim2real/nn_inference_class.py
+    Sim2RealInferenceClass, examples/dce_rl_navigation/sf_inference_class.py NN_Inference_Class; they differ in the observation key
+    alone): `cls(num_envs, num_actions, num_obs, cfg)`, `get_action(obs_dict)`, `reset(env_ids)`, `rnn_states`.  cfg: an object or
+    dict with train_dir and experiment (the checkpoint is <train_dir>/<experiment>/checkpoint_p<policy_index>/), optionally
+    load_checkpoint_kind ('latest', sample-factory's default, or 'best'), policy_index, eval_deterministic and device ('cpu', else the
+    HIP device)."""
+
+    def __init__(self, num_envs, num_actions, num_obs, cfg):
+        import os
+
+        get = cfg.get if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+        for name in ("train_dir", "experiment"):
+            if get(name) is None:
+                raise ValueError(f"cfg has no {name!r}")
+        self.cfg = cfg
+        self.num_agents, self.num_actions, self.num_obs = int(num_envs), int(num_actions), int(num_obs)
+        self.eval_deterministic = bool(get("eval_deterministic", False))
+        self.device = torch.device("cpu" if get("device") == "cpu" else "cuda:0")
+        directory = os.path.join(str(get("train_dir")), str(get("experiment")), f"checkpoint_p{int(get('policy_index', 0) or 0)}")
+        self.actor = RecurrentActor.from_sample_factory_checkpoint(directory, device=str(self.device), kind=get("load_checkpoint_kind", "latest"))
+        if self.actor.obs_dim != self.num_obs or self.actor.action_dim != self.num_actions:
+            raise ValueError(f"the actor of {directory} maps {self.actor.obs_dim} observations to {self.actor.action_dim} actions, not "
+                             f"{self.num_obs} to {self.num_actions}")
+        self.actor.allocate(self.num_agents)
+
+    @property
+    def rnn_states(self):
+        return self.actor.hidden
+
+    def reset(self, env_ids):
+        self.actor.reset(env_ids)
+
+    def get_action(self, obs, get_np=False, get_robot_zero=False):
+        x = obs["obs"] if "obs" in obs else obs["observations"]
+        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+        sample = not self.eval_deterministic
+        eps = torch.randn((x.shape[0], self.num_actions)) if sample and self.device.type == "cpu" else None
+        actions = self.actor(x, sample=sample, eps=eps)
+        if get_robot_zero:
+            actions = actions[0]
+        if get_np:
+            return actions.cpu().numpy()
+        return actions

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 24
+#define AGX_ABI_VERSION 25
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -325,7 +325,8 @@ int agx_update_states(const AgxEnvBuffers *buf, int num_envs, void *stream);
  * atan2(x[i], y[i]), x = the "y" argument).  float64 inside, rounded once: correctly rounded in practice.  Diagnostic
  * entry: the parity tests compare it bit for bit with the CPU restatement.                                          */
 enum { AGX_MATH_SIN = 0, AGX_MATH_COS = 1, AGX_MATH_ATAN2 = 2, AGX_MATH_ASIN = 3, AGX_MATH_EXP = 4,
-       AGX_MATH_EXPM1 = 5 /* expm1_cw: the negative branch of ELU (agx_vae.hip), where torch evaluates expm1 */ };
+       AGX_MATH_EXPM1 = 5 /* expm1_cw: the negative branch of ELU (agx_vae.hip), where torch evaluates expm1 */,
+       AGX_MATH_SIGMOID = 6, AGX_MATH_TANH = 7 /* sigmoid_cw, tanh_cw: the gates of the recurrent cell (agx_policy.hip) */ };
 int agx_math_eval(int which, int n, const float *x, const float *y, float *out, void *stream);
 
 /* Diagnostic: float4 streaming copy of `bytes` (multiple of 16) from src to dst -- the HBM rate a kernel of this library
@@ -1205,7 +1206,7 @@ int agx_state_scatter(const AgxSnapshotTable *table, int num_envs, const void *b
 #define AGX_POLICY_MAX_LAYERS 8
 #define AGX_POLICY_MAX_WIDTH 512
 enum { AGX_POLICY_NONE = 0, AGX_POLICY_ELU = 1 /* alpha 1, expm1_cw on the negative side */, AGX_POLICY_RELU = 2 };
-enum { AGX_POLICY_SAMPLE = 1, AGX_POLICY_CLAMP = 2 };  /* flags of the act call */
+enum { AGX_POLICY_SAMPLE = 1, AGX_POLICY_CLAMP = 2, AGX_POLICY_RESET_AFTER = 4 /* agx_recurrent_act only */ };  /* flags of the act calls */
 typedef struct AgxPolicy AgxPolicy;
 /* Host only: the limits above for dims [num_layers + 1] (what the create call checks first); lds_bytes (optional) receives the
  * dynamic LDS of the launch.                                                                                                */
@@ -1234,6 +1235,55 @@ int agx_policy_act(AgxPolicy *p, int num_envs, const float *obs, float *actions,
 int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
                      void *stream);
 int agx_policy_destroy(AgxPolicy *p);
+
+/* ---- recurrent actor: encoder MLP -> GRU cell -> linear head as one launch (csrc/agx_policy.hip k_recurrent_act) -------------
+ * Replaces sample-factory's actor with a recurrent core as the reference runs it in
+ * examples/dce_rl_navigation/sf_inference_class.py:80-101 and sim2real/nn_inference_class.py:77-101 (normalize_obs, forward_head,
+ * forward_core, forward_tail, then rnn_states kept between calls).  DESIGN.md 3.8.
+ *
+ * The net: observation normaliser (optional); an encoder of L linear layers with the hidden activation after EVERY layer, the
+ * last included (sample-factory's create_mlp); one torch.nn.GRU cell, gate order r, z, n; one linear head of P outputs: P = 2 A
+ * when adaptive_stddev (means, then log-std), P = A with a constant log-std vector (agx_recurrent_set_logstd).
+ *
+ * Numerics: every linear map has the bits of agx_vae_linear (see the policy actor above); the cell per env and channel j < H,
+ * each line one rounded fp32 operation:  r = sigmoid_cw(gi_r + gh_r);  z = sigmoid_cw(gi_z + gh_z);  n = tanh_cw(gi_n + r * gh_n);
+ * a = 1 - z;  b = a * n;  c = z * h;  h' = b + c.  Independent of the batch size, the env's place and other envs' flags.
+ *
+ * Limits: 1 .. AGX_POLICY_MAX_LAYERS - 2 encoder layers; widths as for agx_policy_create (dims[1 .. L] multiples of 32; dims[L] is
+ * the cell's input size); hidden a multiple of 32 within 32 .. AGX_POLICY_MAX_WIDTH; 1 .. 64 actions; the live LDS buffers of 32
+ * envs (the encoder's ping-pong pair, h, gi, gh: (w0 + w1 + 7 hidden) x 128 bytes) within 160 KiB.  Outside them: AGX_E_ARG, the
+ * message names the offending number.                                                                                      */
+typedef struct AgxRecurrent AgxRecurrent;
+/* Host only: the limits above for the encoder widths dims [num_encoder_layers + 1], the hidden size and the head's P;
+ * lds_bytes (optional) receives the dynamic LDS of the launch.                                                              */
+int agx_recurrent_check(int num_encoder_layers, const int32_t *dims, int hidden, int head_out, size_t *lds_bytes);
+/* All arrays are HOST pointers in torch's layouts: enc_weights / enc_biases num_encoder_layers pointers each ([out][in], [out]);
+ * w_ih [3 hidden][dims[L]], w_hh [3 hidden][hidden], b_ih, b_hh [3 hidden] (weight_ih_l0 ... of torch.nn.GRU); head_weight
+ * [P][hidden], head_bias [P].  hidden_activation: AGX_POLICY_ELU or _RELU.  Packing and ownership as agx_policy_create; like it,
+ * create, the setters and destroy are the set-up calls (sf_inference_class.py:40-78 builds and loads the torch module here).  */
+int agx_recurrent_create(int num_encoder_layers, const int32_t *dims, int hidden, int num_actions, int adaptive_stddev,
+                         const float *const *enc_weights, const float *const *enc_biases, const float *w_ih, const float *w_hh,
+                         const float *b_ih, const float *b_hh, const float *head_weight, const float *head_bias, int hidden_activation,
+                         AgxRecurrent **out);
+/* sample-factory's RunningMeanStdInPlace as agx_policy_set_input_norm states rl_games' (sf_inference_class.py:86,
+ * nn_inference_class.py:82 prepare_and_normalize_obs): HOST mean, denom [in]; both NULL: off.                               */
+int agx_recurrent_set_input_norm(AgxRecurrent *p, const float *mean, const float *denom, float clip);
+/* the constant log-std [num_actions] of a head that is not adaptive (action_parameterization.learned_stddev); HOST; NULL: none */
+int agx_recurrent_set_logstd(AgxRecurrent *p, const float *logstd);
+/* One step of the actor for num_envs envs (sf_inference_class.py:80-101 get_action, nn_inference_class.py:77-101): obs [N][in],
+ * hidden [N][hidden] read and written IN PLACE, actions [N][A]; one launch, no allocation, no host synchronisation.
+ * done0, done1 (optional): per-env bytes (torch bool / uint8); an env with either set has its state zeroed BEFORE the cell
+ * (default: what sample-factory's sampler does with the flags of the step that produced obs), or with AGX_POLICY_RESET_AFTER
+ * evaluates with the state it has and STORES zero (dce_nn_navigation.py: get_action, then reset(ids)).
+ * mu_out, logstd_out (optional, [N][A]): the means and the log-std this call used.  AGX_POLICY_SAMPLE / _CLAMP and eps as
+ * agx_policy_act, sigma = exp_cw(logstd); the device generator is the stream of agx_policy_noise.  num_envs = 0 does nothing. */
+int agx_recurrent_act(AgxRecurrent *p, int num_envs, const float *obs, float *hidden, const uint8_t *done0, const uint8_t *done1,
+                      float *actions, float *mu_out, float *logstd_out, const float *eps, int flags, uint64_t rng_seed,
+                      int env_index_base, int env_step, void *stream);
+/* Diagnostic: noise_out [N][A] <- the normals the NULL-eps form draws (the values of agx_policy_noise for A actions).          */
+int agx_recurrent_noise(const AgxRecurrent *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                        void *stream);
+int agx_recurrent_destroy(AgxRecurrent *p);
 
 #ifdef __cplusplus
 }
