@@ -24,6 +24,9 @@ constexpr int kWaves = 4;
 constexpr int kTile = 32;                                    // envs per workgroup
 static_assert(AGX_POLICY_MAX_WIDTH / 32 <= 4 * kWaves, "a wave holds at most four channel tiles (layer_tiles<1 .. 4>)");
 constexpr size_t kLdsLimit = 160 * 1024;
+constexpr int kMaxEncoderLayers = AGX_POLICY_MAX_LAYERS - 2;
+constexpr int kMaxMaps = kMaxEncoderLayers + 3;  // the recurrent actor's: the encoder's layers, then w_ih, w_hh and the head
+static_assert(kMaxMaps == AGX_POLICY_MAX_LAYERS + 1, "the per-map arrays hold every layer either check admits");
 
 struct PolicyK {
   const float *w[AGX_POLICY_MAX_LAYERS];  // packed [k8][cout]
@@ -199,175 +202,6 @@ __global__ void k_policy_noise(int n, int out_dim, uint64_t seed, int env_base, 
   out[i] = policy_normal(seed, env_base + env, step, (int)(i - (long long)env * out_dim));
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-}  // namespace
-
-struct AgxPolicy {
-  int num_layers, activation;
-  int dims[AGX_POLICY_MAX_LAYERS + 1];
-  int k8[AGX_POLICY_MAX_LAYERS], cout[AGX_POLICY_MAX_LAYERS];
-  float *w[AGX_POLICY_MAX_LAYERS], *b[AGX_POLICY_MAX_LAYERS];
-  float *mean, *denom, *logstd;  // device, allocated by create; in use once set
-  bool has_norm, has_logstd;
-  float clip;
-  int buf1;
-  size_t lds_bytes;
-};
-
-extern "C" int agx_policy_destroy(AgxPolicy *p) {
-  if (!p) return AGX_OK;
-  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) {
-    if (p->w[l]) (void)hipFree(p->w[l]);
-    if (p->b[l]) (void)hipFree(p->b[l]);
-  }
-  if (p->mean) (void)hipFree(p->mean);
-  if (p->denom) (void)hipFree(p->denom);
-  if (p->logstd) (void)hipFree(p->logstd);
-  delete p;
-  return AGX_OK;
-}
-
-extern "C" int agx_policy_check(int num_layers, const int32_t *dims, size_t *lds_bytes) {
-  AGX_REQUIRE(dims, "agx_policy_create: null dims");
-  AGX_REQUIRE(num_layers >= 1 && num_layers <= AGX_POLICY_MAX_LAYERS, "agx_policy_create: num_layers = %d, supported: 1 .. %d", num_layers,
-              AGX_POLICY_MAX_LAYERS);
-  AGX_REQUIRE(dims[0] >= 1 && dims[0] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: input width %d, supported: 1 .. %d", dims[0],
-              AGX_POLICY_MAX_WIDTH);
-  for (int l = 1; l < num_layers; ++l)
-    AGX_REQUIRE(dims[l] >= 32 && dims[l] <= AGX_POLICY_MAX_WIDTH && dims[l] % 32 == 0,
-                "agx_policy_create: hidden width %d (output of layer %d): a multiple of 32 up to %d is supported", dims[l], l - 1,
-                AGX_POLICY_MAX_WIDTH);
-  AGX_REQUIRE(dims[num_layers] >= 1 && dims[num_layers] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: output width %d, supported: 1 .. %d",
-              dims[num_layers], AGX_POLICY_MAX_WIDTH);
-  // activation a (0 = the input .. num_layers = the mean) lives in buffer a & 1
-  int width[2] = {0, 0};
-  for (int a = 0; a <= num_layers; ++a) {
-    const int wa = a == 0 ? round_up(dims[0], 8) : (a == num_layers ? round_up(dims[a], 32) : dims[a]);
-    if (wa > width[a & 1]) width[a & 1] = wa;
-  }
-  const size_t bytes = (size_t)(width[0] + width[1]) * kTile * sizeof(float);
-  AGX_REQUIRE(bytes <= kLdsLimit, "agx_policy_create: activations of widths %d + %d for 32 envs need %zu bytes of LDS, a workgroup has %zu",
-              width[0], width[1], bytes, kLdsLimit);
-  if (lds_bytes) *lds_bytes = bytes;
-  return AGX_OK;
-}
-
-extern "C" int agx_policy_create(int num_layers, const int32_t *dims, const float *const *weights, const float *const *biases,
-                                 int hidden_activation, AgxPolicy **out) {
-  AGX_REQUIRE(out, "agx_policy_create: null handle pointer");
-  *out = nullptr;
-  AGX_REQUIRE(dims && weights && biases, "agx_policy_create: null argument");
-  size_t lds_bytes = 0;
-  if (int e = agx_policy_check(num_layers, dims, &lds_bytes)) return e;
-  AGX_REQUIRE(hidden_activation == AGX_POLICY_NONE || hidden_activation == AGX_POLICY_ELU || hidden_activation == AGX_POLICY_RELU,
-              "agx_policy_create: hidden_activation = %d (AGX_POLICY_NONE, _ELU or _RELU)", hidden_activation);
-  for (int l = 0; l < num_layers; ++l) AGX_REQUIRE(weights[l] && biases[l], "agx_policy_create: layer %d: null weight or bias", l);
-  AgxPolicy *p = new AgxPolicy();
-  p->num_layers = num_layers;
-  p->activation = hidden_activation;
-  for (int l = 0; l <= num_layers; ++l) p->dims[l] = dims[l];
-  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) { p->w[l] = p->b[l] = nullptr; p->k8[l] = p->cout[l] = 0; }
-  p->mean = p->denom = p->logstd = nullptr;
-  p->has_norm = p->has_logstd = false;
-  p->clip = 0.0f;
-  p->lds_bytes = lds_bytes;
-  int width0 = 0;
-  for (int a = 0; a <= num_layers; a += 2) {
-    const int wa = a == 0 ? round_up(dims[0], 8) : (a == num_layers ? round_up(dims[a], 32) : dims[a]);
-    if (wa > width0) width0 = wa;
-  }
-  p->buf1 = width0 * kTile;
-  hipError_t e = hipSuccess;
-  for (int l = 0; l < num_layers && e == hipSuccess; ++l) {
-    const int k = dims[l], co = dims[l + 1];
-    const int cop = l + 1 == num_layers ? round_up(co, 32) : co;
-    p->k8[l] = round_up(k, 8);
-    p->cout[l] = cop;
-    // the last layer's rows past `co` are zero weights and zero biases: padding the caller never sees
-    std::vector<float> padded((size_t)cop * k, 0.0f), bias((size_t)cop, 0.0f);
-    for (size_t i = 0; i < (size_t)co * k; ++i) padded[i] = weights[l][i];
-    for (int i = 0; i < co; ++i) bias[i] = biases[l][i];
-    std::vector<float> packed(agx_vae_packed_floats(cop, k));
-    agx_vae_pack_weight(cop, k, padded.data(), packed.data());
-    e = hipMalloc((void **)&p->w[l], packed.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->b[l], bias.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void **)&p->mean, (size_t)dims[0] * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&p->denom, (size_t)dims[0] * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&p->logstd, (size_t)dims[num_layers] * sizeof(float));
-  // above 64 KiB of dynamic LDS the runtime may want to be told; a runtime that refuses the attribute refuses the launch too,
-  // and says so there
-  if (e == hipSuccess && lds_bytes > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void *)k_policy_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    (void)hipGetLastError();
-  }
-  if (e != hipSuccess) {
-    agx_policy_destroy(p);
-    (void)hipGetLastError();
-    return fail(AGX_E_LAUNCH, "agx_policy_create: %s", hipGetErrorString(e));
-  }
-  *out = p;
-  return AGX_OK;
-}
-
-extern "C" int agx_policy_set_input_norm(AgxPolicy *p, const float *mean, const float *denom, float clip) {
-  AGX_REQUIRE(p, "agx_policy_set_input_norm: null handle");
-  if (!mean && !denom) { p->has_norm = false; return AGX_OK; }
-  AGX_REQUIRE(mean && denom, "agx_policy_set_input_norm: mean and denom come together");
-  AGX_REQUIRE(clip > 0.0f, "agx_policy_set_input_norm: clip = %g must be positive", (double)clip);
-  hipError_t e = hipMemcpy(p->mean, mean, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->denom, denom, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_policy_set_input_norm: %s", hipGetErrorString(e));
-  p->clip = clip;
-  p->has_norm = true;
-  return AGX_OK;
-}
-
-extern "C" int agx_policy_set_logstd(AgxPolicy *p, const float *logstd) {
-  AGX_REQUIRE(p, "agx_policy_set_logstd: null handle");
-  if (!logstd) { p->has_logstd = false; return AGX_OK; }
-  hipError_t e = hipMemcpy(p->logstd, logstd, (size_t)p->dims[p->num_layers] * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_policy_set_logstd: %s", hipGetErrorString(e));
-  p->has_logstd = true;
-  return AGX_OK;
-}
-
-extern "C" int agx_policy_act(AgxPolicy *p, int num_envs, const float *obs, float *actions, float *mu_out, const float *eps, int flags,
-                              uint64_t rng_seed, int env_index_base, int env_step, void *stream) {
-  AGX_REQUIRE(p, "agx_policy_act: null handle");
-  AGX_REQUIRE(num_envs >= 0 && num_envs <= (1 << 22), "agx_policy_act: num_envs = %d, supported: 0 .. %d", num_envs, 1 << 22);
-  AGX_REQUIRE((flags & ~(AGX_POLICY_SAMPLE | AGX_POLICY_CLAMP)) == 0, "agx_policy_act: flags = %d", flags);
-  AGX_REQUIRE(!(flags & AGX_POLICY_SAMPLE) || p->has_logstd, "agx_policy_act: AGX_POLICY_SAMPLE needs a logstd (agx_policy_set_logstd)");
-  if (num_envs == 0) return AGX_OK;
-  AGX_REQUIRE(obs, "agx_policy_act: null obs");
-  AGX_REQUIRE(actions, "agx_policy_act: null actions");
-  PolicyK a;
-  for (int l = 0; l < AGX_POLICY_MAX_LAYERS; ++l) { a.w[l] = p->w[l]; a.b[l] = p->b[l]; a.k8[l] = p->k8[l]; a.cout[l] = p->cout[l]; }
-  a.num_layers = p->num_layers; a.in_dim = p->dims[0]; a.out_dim = p->dims[p->num_layers]; a.activation = p->activation;
-  a.obs = obs; a.eps = eps; a.logstd = p->logstd;
-  a.mean = p->has_norm ? p->mean : nullptr; a.denom = p->has_norm ? p->denom : nullptr;
-  a.actions = actions; a.mu_out = mu_out;
-  a.clip = p->clip;
-  a.n = num_envs; a.flags = flags; a.env_base = env_index_base; a.step = env_step;
-  a.buf1 = p->buf1;
-  a.seed = rng_seed;
-  hipLaunchKernelGGL(k_policy_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->lds_bytes, (hipStream_t)stream, a);
-  return check_launch("agx_policy_act");
-}
-
-extern "C" int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
-                                void *stream) {
-  AGX_REQUIRE(p && noise_out, "agx_policy_noise: null argument");
-  AGX_REQUIRE(num_envs > 0 && num_envs <= (1 << 22), "agx_policy_noise: num_envs = %d, supported: 1 .. %d", num_envs, 1 << 22);
-  const int out_dim = p->dims[p->num_layers];
-  const long long total = (long long)num_envs * out_dim;
-  hipLaunchKernelGGL(k_policy_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, out_dim, rng_seed,
-                     env_index_base, env_step, noise_out);
-  return check_launch("agx_policy_noise");
-}
-
 // ---- recurrent actor: encoder MLP -> GRU cell -> linear head as ONE launch ----------------------------------------------------
 // sample-factory's actor with a recurrent core (sf_inference_class.py:80-101, nn_inference_class.py:77-101).  The mapping of
 // k_policy_act: a workgroup of four waves owns 32 envs, every linear map is layer_tiles.  LDS, in floats per env column:
@@ -375,11 +209,10 @@ extern "C" int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_s
 //   [h]            H: the state of the tile, h' in place after the gates
 //   [gi | gh]      3H each: W_ih x + b_ih and W_hh h + b_hh, gate order r, z, n; afterwards the head's output (<= 128 <= 6H rows)
 // Nothing crosses workgroups: a tile reads its rows of the state buffer before the gates and writes them after.
-namespace {
-constexpr int kMaxEncoderLayers = AGX_POLICY_MAX_LAYERS - 2;
-constexpr int kMaxMaps = kMaxEncoderLayers + 3;  // the encoder's layers, then w_ih, w_hh and the head
-static_assert(kMaxMaps == AGX_POLICY_MAX_LAYERS + 1, "the per-map arrays hold every encoder layer the check admits plus three");
-
+// The observation loop, the sampling epilogue and the layer dispatch are stated here a second time on purpose: one workgroup's chain
+// of layers is the call's latency, and any change to this kernel's text reschedules it.  Shared device functions cost k_recurrent_act
+// 0.15 to 0.37 us per call (sharing the observation loop alone: 0.16 to 0.28), and k_policy_act through run_layer needs 208 VGPRs
+// instead of 178 (profiles/policy_refactor_codegen.md, profiles/policy_refactor_ab.json).
 struct RecurrentK {
   const float *w[kMaxMaps];  // encoder layers 0 .. L-1, then w_ih, w_hh, head: packed [k8][cout]
   const float *b[kMaxMaps];
@@ -509,43 +342,227 @@ __global__ void __launch_bounds__(64 * kWaves) k_recurrent_act(RecurrentK a) {
     if (a.logstd_out && have_ls) a.logstd_out[out0 + i] = ls;
   }
 }
-}  // namespace
 
-struct AgxRecurrent {
-  int num_encoder_layers, activation, hidden, num_actions, adaptive;
-  int dims[kMaxEncoderLayers + 1];  // the encoder's widths
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// ---- the host side both actors share.  `entry` is the name of the C entry a message begins with ---------------------------------
+struct ActorCommon {
+  float *w[kMaxMaps], *b[kMaxMaps];  // device; a null entry is a map the actor does not have
   int k8[kMaxMaps], cout[kMaxMaps];
-  float *w[kMaxMaps], *b[kMaxMaps];  // encoder, w_ih, w_hh, head
-  float *mean, *denom, *logstd;
+  float *mean, *denom, *logstd;  // device, allocated by create; in use once set
   bool has_norm, has_logstd;
   float clip;
-  int buf1, off_h, off_gi;
+  int in_dim, num_actions;
+  int buf1;
   size_t lds_bytes;
 };
 
-extern "C" int agx_recurrent_destroy(AgxRecurrent *p) {
-  if (!p) return AGX_OK;
-  for (int l = 0; l < kMaxMaps; ++l) {
-    if (p->w[l]) (void)hipFree(p->w[l]);
-    if (p->b[l]) (void)hipFree(p->b[l]);
+// floats per env column of the two ping-pong buffers: activation a (0 = the input, padded to 8, .. count = the last map's output,
+// padded to 32 when pad_last) lives in buffer a & 1.  The one statement of that rule
+void pingpong_widths(int count, const int32_t *dims, bool pad_last, int width[2]) {
+  width[0] = width[1] = 0;
+  for (int a = 0; a <= count; ++a) {
+    const int wa = a == 0 ? round_up(dims[0], 8) : (a == count && pad_last ? round_up(dims[a], 32) : dims[a]);
+    if (wa > width[a & 1]) width[a & 1] = wa;
   }
-  if (p->mean) (void)hipFree(p->mean);
-  if (p->denom) (void)hipFree(p->denom);
-  if (p->logstd) (void)hipFree(p->logstd);
+}
+
+// map l = torch's w [co][k] and b [co]: the rows padded to a multiple of 32 with zero weights and zero biases (padding the caller
+// never sees; hidden widths are multiples of 32 already), packed [k8][cout], on the device
+hipError_t upload_map(ActorCommon &c, int l, int co, int k, const float *w, const float *b) {
+  const int cop = round_up(co, 32);
+  c.k8[l] = round_up(k, 8);
+  c.cout[l] = cop;
+  std::vector<float> padded((size_t)cop * k, 0.0f), bias((size_t)cop, 0.0f);
+  for (size_t i = 0; i < (size_t)co * k; ++i) padded[i] = w[i];
+  for (int i = 0; i < co; ++i) bias[i] = b[i];
+  std::vector<float> packed(agx_vae_packed_floats(cop, k));
+  agx_vae_pack_weight(cop, k, padded.data(), packed.data());
+  hipError_t e = hipMalloc((void **)&c.w[l], packed.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&c.b[l], bias.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(c.w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(c.b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
+  return e;
+}
+
+// what a create does once its maps are up: the normaliser's and the log-std's buffers, and the kernel's dynamic-LDS attribute
+hipError_t finish_create(ActorCommon &c, const void *kernel) {
+  hipError_t e = hipMalloc((void **)&c.mean, (size_t)c.in_dim * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&c.denom, (size_t)c.in_dim * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&c.logstd, (size_t)c.num_actions * sizeof(float));
+  // above 64 KiB of dynamic LDS the runtime may want to be told; a runtime that refuses the attribute refuses the launch too, and
+  // says so there.  The attribute belongs to the kernel, not to this actor: always the limit the checks admit, so that a smaller
+  // actor created later does not lower it under an earlier one
+  if (e == hipSuccess) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
+    (void)hipGetLastError();
+  }
+  return e;
+}
+
+void free_actor(ActorCommon &c) {
+  for (int l = 0; l < kMaxMaps; ++l) {
+    if (c.w[l]) (void)hipFree(c.w[l]);
+    if (c.b[l]) (void)hipFree(c.b[l]);
+  }
+  if (c.mean) (void)hipFree(c.mean);
+  if (c.denom) (void)hipFree(c.denom);
+  if (c.logstd) (void)hipFree(c.logstd);
+}
+
+int set_input_norm(const char *entry, ActorCommon &c, const float *mean, const float *denom, float clip) {
+  if (!mean && !denom) { c.has_norm = false; return AGX_OK; }
+  AGX_REQUIRE(mean && denom, "%s: mean and denom come together", entry);
+  AGX_REQUIRE(clip > 0.0f, "%s: clip = %g must be positive", entry, (double)clip);
+  hipError_t e = hipMemcpy(c.mean, mean, (size_t)c.in_dim * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(c.denom, denom, (size_t)c.in_dim * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "%s: %s", entry, hipGetErrorString(e));
+  c.clip = clip;
+  c.has_norm = true;
+  return AGX_OK;
+}
+
+int set_logstd(const char *entry, ActorCommon &c, const float *logstd) {
+  if (!logstd) { c.has_logstd = false; return AGX_OK; }
+  hipError_t e = hipMemcpy(c.logstd, logstd, (size_t)c.num_actions * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "%s: %s", entry, hipGetErrorString(e));
+  c.has_logstd = true;
+  return AGX_OK;
+}
+
+int launch_noise(const char *entry, const ActorCommon *c, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                 void *stream) {
+  AGX_REQUIRE(c && noise_out, "%s: null argument", entry);
+  AGX_REQUIRE(num_envs > 0 && num_envs <= (1 << 22), "%s: num_envs = %d, supported: 1 .. %d", entry, num_envs, 1 << 22);
+  const long long total = (long long)num_envs * c->num_actions;
+  hipLaunchKernelGGL(k_policy_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, c->num_actions, rng_seed,
+                     env_index_base, env_step, noise_out);
+  return check_launch(entry);
+}
+
+// the fields PolicyK and RecurrentK have in common
+template <class K>
+void fill_common(K &a, const ActorCommon &c, int num_envs, const float *obs, float *actions, float *mu_out, const float *eps, int flags,
+                 uint64_t rng_seed, int env_index_base, int env_step) {
+  for (size_t l = 0; l < sizeof(a.w) / sizeof(a.w[0]); ++l) { a.w[l] = c.w[l]; a.b[l] = c.b[l]; a.k8[l] = c.k8[l]; a.cout[l] = c.cout[l]; }
+  a.in_dim = c.in_dim;
+  a.obs = obs; a.eps = eps; a.logstd = c.has_logstd ? c.logstd : nullptr;
+  a.mean = c.has_norm ? c.mean : nullptr; a.denom = c.has_norm ? c.denom : nullptr;
+  a.actions = actions; a.mu_out = mu_out;
+  a.clip = c.clip;
+  a.n = num_envs; a.flags = flags; a.env_base = env_index_base; a.step = env_step;
+  a.buf1 = c.buf1;
+  a.seed = rng_seed;
+}
+}  // namespace
+
+struct AgxPolicy {
+  ActorCommon c;
+  int num_layers, activation;
+};
+
+struct AgxRecurrent {
+  ActorCommon c;
+  int num_encoder_layers, activation, hidden, adaptive;
+  int off_h, off_gi;
+};
+
+extern "C" int agx_policy_destroy(AgxPolicy *p) {
+  if (!p) return AGX_OK;
+  free_actor(p->c);
   delete p;
   return AGX_OK;
 }
 
-namespace {
-// floats per env column of the encoder's two ping-pong buffers: activation a (0 = the input .. L = the cell's input) in buffer a & 1
-void recurrent_widths(int L, const int32_t *dims, int width[2]) {
-  width[0] = width[1] = 0;
-  for (int a = 0; a <= L; ++a) {
-    const int wa = a == 0 ? round_up(dims[0], 8) : dims[a];
-    if (wa > width[a & 1]) width[a & 1] = wa;
-  }
+extern "C" int agx_policy_check(int num_layers, const int32_t *dims, size_t *lds_bytes) {
+  AGX_REQUIRE(dims, "agx_policy_create: null dims");
+  AGX_REQUIRE(num_layers >= 1 && num_layers <= AGX_POLICY_MAX_LAYERS, "agx_policy_create: num_layers = %d, supported: 1 .. %d", num_layers,
+              AGX_POLICY_MAX_LAYERS);
+  AGX_REQUIRE(dims[0] >= 1 && dims[0] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: input width %d, supported: 1 .. %d", dims[0],
+              AGX_POLICY_MAX_WIDTH);
+  for (int l = 1; l < num_layers; ++l)
+    AGX_REQUIRE(dims[l] >= 32 && dims[l] <= AGX_POLICY_MAX_WIDTH && dims[l] % 32 == 0,
+                "agx_policy_create: hidden width %d (output of layer %d): a multiple of 32 up to %d is supported", dims[l], l - 1,
+                AGX_POLICY_MAX_WIDTH);
+  AGX_REQUIRE(dims[num_layers] >= 1 && dims[num_layers] <= AGX_POLICY_MAX_WIDTH, "agx_policy_create: output width %d, supported: 1 .. %d",
+              dims[num_layers], AGX_POLICY_MAX_WIDTH);
+  int width[2];
+  pingpong_widths(num_layers, dims, true, width);  // activation num_layers is the mean
+  const size_t bytes = (size_t)(width[0] + width[1]) * kTile * sizeof(float);
+  AGX_REQUIRE(bytes <= kLdsLimit, "agx_policy_create: activations of widths %d + %d for 32 envs need %zu bytes of LDS, a workgroup has %zu",
+              width[0], width[1], bytes, kLdsLimit);
+  if (lds_bytes) *lds_bytes = bytes;
+  return AGX_OK;
 }
-}  // namespace
+
+extern "C" int agx_policy_create(int num_layers, const int32_t *dims, const float *const *weights, const float *const *biases,
+                                 int hidden_activation, AgxPolicy **out) {
+  AGX_REQUIRE(out, "agx_policy_create: null handle pointer");
+  *out = nullptr;
+  AGX_REQUIRE(dims && weights && biases, "agx_policy_create: null argument");
+  size_t lds_bytes = 0;
+  if (int e = agx_policy_check(num_layers, dims, &lds_bytes)) return e;
+  AGX_REQUIRE(hidden_activation == AGX_POLICY_NONE || hidden_activation == AGX_POLICY_ELU || hidden_activation == AGX_POLICY_RELU,
+              "agx_policy_create: hidden_activation = %d (AGX_POLICY_NONE, _ELU or _RELU)", hidden_activation);
+  for (int l = 0; l < num_layers; ++l) AGX_REQUIRE(weights[l] && biases[l], "agx_policy_create: layer %d: null weight or bias", l);
+  AgxPolicy *p = new AgxPolicy();  // zeros and null pointers
+  p->num_layers = num_layers;
+  p->activation = hidden_activation;
+  p->c.in_dim = dims[0];
+  p->c.num_actions = dims[num_layers];
+  p->c.lds_bytes = lds_bytes;
+  int width[2];
+  pingpong_widths(num_layers, dims, true, width);
+  p->c.buf1 = width[0] * kTile;
+  hipError_t e = hipSuccess;
+  for (int l = 0; l < num_layers && e == hipSuccess; ++l) e = upload_map(p->c, l, dims[l + 1], dims[l], weights[l], biases[l]);
+  if (e == hipSuccess) e = finish_create(p->c, (const void *)k_policy_act);
+  if (e != hipSuccess) {
+    agx_policy_destroy(p);
+    (void)hipGetLastError();
+    return fail(AGX_E_LAUNCH, "agx_policy_create: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return AGX_OK;
+}
+
+extern "C" int agx_policy_set_input_norm(AgxPolicy *p, const float *mean, const float *denom, float clip) {
+  AGX_REQUIRE(p, "agx_policy_set_input_norm: null handle");
+  return set_input_norm("agx_policy_set_input_norm", p->c, mean, denom, clip);
+}
+
+extern "C" int agx_policy_set_logstd(AgxPolicy *p, const float *logstd) {
+  AGX_REQUIRE(p, "agx_policy_set_logstd: null handle");
+  return set_logstd("agx_policy_set_logstd", p->c, logstd);
+}
+
+extern "C" int agx_policy_act(AgxPolicy *p, int num_envs, const float *obs, float *actions, float *mu_out, const float *eps, int flags,
+                              uint64_t rng_seed, int env_index_base, int env_step, void *stream) {
+  AGX_REQUIRE(p, "agx_policy_act: null handle");
+  AGX_REQUIRE(num_envs >= 0 && num_envs <= (1 << 22), "agx_policy_act: num_envs = %d, supported: 0 .. %d", num_envs, 1 << 22);
+  AGX_REQUIRE((flags & ~(AGX_POLICY_SAMPLE | AGX_POLICY_CLAMP)) == 0, "agx_policy_act: flags = %d", flags);
+  AGX_REQUIRE(!(flags & AGX_POLICY_SAMPLE) || p->c.has_logstd, "agx_policy_act: AGX_POLICY_SAMPLE needs a logstd (agx_policy_set_logstd)");
+  if (num_envs == 0) return AGX_OK;
+  AGX_REQUIRE(obs, "agx_policy_act: null obs");
+  AGX_REQUIRE(actions, "agx_policy_act: null actions");
+  PolicyK a;
+  fill_common(a, p->c, num_envs, obs, actions, mu_out, eps, flags, rng_seed, env_index_base, env_step);
+  a.num_layers = p->num_layers; a.out_dim = p->c.num_actions; a.activation = p->activation;
+  hipLaunchKernelGGL(k_policy_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->c.lds_bytes, (hipStream_t)stream, a);
+  return check_launch("agx_policy_act");
+}
+
+extern "C" int agx_policy_noise(const AgxPolicy *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
+                                void *stream) {
+  return launch_noise("agx_policy_noise", p ? &p->c : nullptr, num_envs, rng_seed, env_index_base, env_step, noise_out, stream);
+}
+
+extern "C" int agx_recurrent_destroy(AgxRecurrent *p) {
+  if (!p) return AGX_OK;
+  free_actor(p->c);
+  delete p;
+  return AGX_OK;
+}
 
 extern "C" int agx_recurrent_check(int num_encoder_layers, const int32_t *dims, int hidden, int head_out, size_t *lds_bytes) {
   const int L = num_encoder_layers;
@@ -562,7 +579,7 @@ extern "C" int agx_recurrent_check(int num_encoder_layers, const int32_t *dims, 
   AGX_REQUIRE(head_out >= 1 && head_out <= 128, "agx_recurrent_create: head width %d, supported: 1 .. 128 (64 actions, means and log-std)",
               head_out);
   int width[2];
-  recurrent_widths(L, dims, width);
+  pingpong_widths(L, dims, false, width);  // activation L is the cell's input
   // x (the ping-pong pair), h, gi and gh are live together in the cell
   const size_t bytes = (size_t)(width[0] + width[1] + 7 * hidden) * kTile * sizeof(float);
   AGX_REQUIRE(bytes <= kLdsLimit,
@@ -588,49 +605,23 @@ extern "C" int agx_recurrent_create(int num_encoder_layers, const int32_t *dims,
   AGX_REQUIRE(hidden_activation == AGX_POLICY_ELU || hidden_activation == AGX_POLICY_RELU,
               "agx_recurrent_create: hidden_activation = %d (AGX_POLICY_ELU or _RELU)", hidden_activation);
   for (int l = 0; l < L; ++l) AGX_REQUIRE(enc_weights[l] && enc_biases[l], "agx_recurrent_create: encoder layer %d: null weight or bias", l);
-  AgxRecurrent *p = new AgxRecurrent();
-  p->num_encoder_layers = L; p->activation = hidden_activation; p->hidden = H; p->num_actions = num_actions; p->adaptive = adaptive_stddev ? 1 : 0;
-  for (int l = 0; l <= L; ++l) p->dims[l] = dims[l];
-  for (int l = 0; l < kMaxMaps; ++l) { p->w[l] = p->b[l] = nullptr; p->k8[l] = p->cout[l] = 0; }
-  p->mean = p->denom = p->logstd = nullptr;
-  p->has_norm = p->has_logstd = false;
-  p->clip = 0.0f;
-  p->lds_bytes = lds_bytes;
+  AgxRecurrent *p = new AgxRecurrent();  // zeros and null pointers
+  p->num_encoder_layers = L; p->activation = hidden_activation; p->hidden = H; p->adaptive = adaptive_stddev ? 1 : 0;
+  p->c.in_dim = dims[0];
+  p->c.num_actions = num_actions;
+  p->c.lds_bytes = lds_bytes;
   int width[2];
-  recurrent_widths(L, dims, width);
-  p->buf1 = width[0] * kTile;
+  pingpong_widths(L, dims, false, width);
+  p->c.buf1 = width[0] * kTile;
   p->off_h = (width[0] + width[1]) * kTile;
   p->off_gi = p->off_h + H * kTile;
   hipError_t e = hipSuccess;
   static_assert(kMaxEncoderLayers + 3 <= kMaxMaps, "map L + 2 (the head) is the last entry");
-  for (int l = 0; l < L + 3 && e == hipSuccess; ++l) {
-    // rows, columns and the host arrays of map l: the encoder's layers, W_ih [3H][I], W_hh [3H][H], the head [P][H]
-    const int k = l < L ? dims[l] : (l == L ? dims[L] : H);
-    const int co = l < L ? dims[l + 1] : (l < L + 2 ? 3 * H : P);
-    const float *wsrc = l < L ? enc_weights[l] : (l == L ? w_ih : (l == L + 1 ? w_hh : head_weight));
-    const float *bsrc = l < L ? enc_biases[l] : (l == L ? b_ih : (l == L + 1 ? b_hh : head_bias));
-    const int cop = round_up(co, 32);  // only the head is padded: zero weights and zero biases the caller never sees
-    p->k8[l] = round_up(k, 8);
-    p->cout[l] = cop;
-    std::vector<float> padded((size_t)cop * k, 0.0f), bias((size_t)cop, 0.0f);
-    for (size_t i = 0; i < (size_t)co * k; ++i) padded[i] = wsrc[i];
-    for (int i = 0; i < co; ++i) bias[i] = bsrc[i];
-    std::vector<float> packed(agx_vae_packed_floats(cop, k));
-    agx_vae_pack_weight(cop, k, padded.data(), packed.data());
-    e = hipMalloc((void **)&p->w[l], packed.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->b[l], bias.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->b[l], bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void **)&p->mean, (size_t)dims[0] * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&p->denom, (size_t)dims[0] * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&p->logstd, (size_t)num_actions * sizeof(float));
-  // above 64 KiB of dynamic LDS the runtime may want to be told.  The attribute belongs to the kernel, not to this actor: always
-  // the limit the check admits, so that a smaller actor created later does not lower it under an earlier one
-  if (e == hipSuccess) {
-    (void)hipFuncSetAttribute((const void *)k_recurrent_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-    (void)hipGetLastError();
-  }
+  for (int l = 0; l < L && e == hipSuccess; ++l) e = upload_map(p->c, l, dims[l + 1], dims[l], enc_weights[l], enc_biases[l]);
+  if (e == hipSuccess) e = upload_map(p->c, L, 3 * H, dims[L], w_ih, b_ih);
+  if (e == hipSuccess) e = upload_map(p->c, L + 1, 3 * H, H, w_hh, b_hh);
+  if (e == hipSuccess) e = upload_map(p->c, L + 2, P, H, head_weight, head_bias);
+  if (e == hipSuccess) e = finish_create(p->c, (const void *)k_recurrent_act);
   if (e != hipSuccess) {
     agx_recurrent_destroy(p);
     (void)hipGetLastError();
@@ -642,25 +633,13 @@ extern "C" int agx_recurrent_create(int num_encoder_layers, const int32_t *dims,
 
 extern "C" int agx_recurrent_set_input_norm(AgxRecurrent *p, const float *mean, const float *denom, float clip) {
   AGX_REQUIRE(p, "agx_recurrent_set_input_norm: null handle");
-  if (!mean && !denom) { p->has_norm = false; return AGX_OK; }
-  AGX_REQUIRE(mean && denom, "agx_recurrent_set_input_norm: mean and denom come together");
-  AGX_REQUIRE(clip > 0.0f, "agx_recurrent_set_input_norm: clip = %g must be positive", (double)clip);
-  hipError_t e = hipMemcpy(p->mean, mean, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->denom, denom, (size_t)p->dims[0] * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_recurrent_set_input_norm: %s", hipGetErrorString(e));
-  p->clip = clip;
-  p->has_norm = true;
-  return AGX_OK;
+  return set_input_norm("agx_recurrent_set_input_norm", p->c, mean, denom, clip);
 }
 
 extern "C" int agx_recurrent_set_logstd(AgxRecurrent *p, const float *logstd) {
   AGX_REQUIRE(p, "agx_recurrent_set_logstd: null handle");
   AGX_REQUIRE(!p->adaptive, "agx_recurrent_set_logstd: the head is adaptive: it emits the log-std itself");
-  if (!logstd) { p->has_logstd = false; return AGX_OK; }
-  hipError_t e = hipMemcpy(p->logstd, logstd, (size_t)p->num_actions * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(AGX_E_LAUNCH, "agx_recurrent_set_logstd: %s", hipGetErrorString(e));
-  p->has_logstd = true;
-  return AGX_OK;
+  return set_logstd("agx_recurrent_set_logstd", p->c, logstd);
 }
 
 extern "C" int agx_recurrent_act(AgxRecurrent *p, int num_envs, const float *obs, float *hidden, const uint8_t *done0, const uint8_t *done1,
@@ -669,7 +648,7 @@ extern "C" int agx_recurrent_act(AgxRecurrent *p, int num_envs, const float *obs
   AGX_REQUIRE(p, "agx_recurrent_act: null handle");
   AGX_REQUIRE(num_envs >= 0 && num_envs <= (1 << 22), "agx_recurrent_act: num_envs = %d, supported: 0 .. %d", num_envs, 1 << 22);
   AGX_REQUIRE((flags & ~(AGX_POLICY_SAMPLE | AGX_POLICY_CLAMP | AGX_POLICY_RESET_AFTER)) == 0, "agx_recurrent_act: flags = %d", flags);
-  const bool have_logstd = p->adaptive || p->has_logstd;
+  const bool have_logstd = p->adaptive || p->c.has_logstd;
   AGX_REQUIRE(!(flags & AGX_POLICY_SAMPLE) || have_logstd,
               "agx_recurrent_act: AGX_POLICY_SAMPLE needs a logstd (an adaptive head or agx_recurrent_set_logstd)");
   AGX_REQUIRE(!logstd_out || have_logstd, "agx_recurrent_act: logstd_out needs a logstd (an adaptive head or agx_recurrent_set_logstd)");
@@ -678,27 +657,17 @@ extern "C" int agx_recurrent_act(AgxRecurrent *p, int num_envs, const float *obs
   AGX_REQUIRE(hidden, "agx_recurrent_act: null hidden");
   AGX_REQUIRE(actions, "agx_recurrent_act: null actions");
   RecurrentK a;
-  for (int l = 0; l < kMaxMaps; ++l) { a.w[l] = p->w[l]; a.b[l] = p->b[l]; a.k8[l] = p->k8[l]; a.cout[l] = p->cout[l]; }
-  a.num_encoder_layers = p->num_encoder_layers; a.in_dim = p->dims[0]; a.hidden = p->hidden; a.num_actions = p->num_actions;
+  fill_common(a, p->c, num_envs, obs, actions, mu_out, eps, flags, rng_seed, env_index_base, env_step);
+  a.num_encoder_layers = p->num_encoder_layers; a.hidden = p->hidden; a.num_actions = p->c.num_actions;
   a.adaptive = p->adaptive; a.activation = p->activation;
-  a.obs = obs; a.eps = eps; a.logstd = p->has_logstd ? p->logstd : nullptr;
-  a.mean = p->has_norm ? p->mean : nullptr; a.denom = p->has_norm ? p->denom : nullptr;
   a.done0 = done0; a.done1 = done1;
-  a.state = hidden; a.actions = actions; a.mu_out = mu_out; a.logstd_out = logstd_out;
-  a.clip = p->clip;
-  a.n = num_envs; a.flags = flags; a.env_base = env_index_base; a.step = env_step;
-  a.buf1 = p->buf1; a.off_h = p->off_h; a.off_gi = p->off_gi;
-  a.seed = rng_seed;
-  hipLaunchKernelGGL(k_recurrent_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->lds_bytes, (hipStream_t)stream, a);
+  a.state = hidden; a.logstd_out = logstd_out;
+  a.off_h = p->off_h; a.off_gi = p->off_gi;
+  hipLaunchKernelGGL(k_recurrent_act, dim3((unsigned)((num_envs + kTile - 1) / kTile)), dim3(64 * kWaves), p->c.lds_bytes, (hipStream_t)stream, a);
   return check_launch("agx_recurrent_act");
 }
 
 extern "C" int agx_recurrent_noise(const AgxRecurrent *p, int num_envs, uint64_t rng_seed, int env_index_base, int env_step, float *noise_out,
                                    void *stream) {
-  AGX_REQUIRE(p && noise_out, "agx_recurrent_noise: null argument");
-  AGX_REQUIRE(num_envs > 0 && num_envs <= (1 << 22), "agx_recurrent_noise: num_envs = %d, supported: 1 .. %d", num_envs, 1 << 22);
-  const long long total = (long long)num_envs * p->num_actions;
-  hipLaunchKernelGGL(k_policy_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, num_envs, p->num_actions, rng_seed,
-                     env_index_base, env_step, noise_out);
-  return check_launch("agx_recurrent_noise");
+  return launch_noise("agx_recurrent_noise", p ? &p->c : nullptr, num_envs, rng_seed, env_index_base, env_step, noise_out, stream);
 }

@@ -20,6 +20,15 @@ NORM_CLIP = 5.0      # ... clamped to +-5
 _IGNORED_PREFIXES = ("a2c_network.value.", "a2c_network.critic_mlp.", "value_mean_std.", "running_mean_std.count")
 
 
+def _arr(a):
+    return np.ascontiguousarray(np.asarray(a, np.float32))
+
+
+def _f32(t):
+    """a checkpoint's tensor as contiguous float32 numpy"""
+    return np.ascontiguousarray(torch.as_tensor(t).detach().to("cpu", torch.float32).contiguous().numpy())
+
+
 def check_dims(dims):
     """the limits of agx_policy_create for layer widths [in, hidden..., out] (ValueError names the offending number); returns the
     bytes of LDS a workgroup uses.  Host only: works without a GPU."""
@@ -73,51 +82,45 @@ def actor_arrays_from_state_dict(sd):
             key = f"{name}.{kind}"
             if key not in sd:
                 raise KeyError(f"rl_games checkpoint has no {key!r} (layers found: {sorted(layers)}, then a2c_network.mu)")
-            dst.append(torch.as_tensor(sd[key]).detach().to("cpu", torch.float32).contiguous().numpy())
-    logstd = None
-    if "a2c_network.sigma" in sd:
-        logstd = torch.as_tensor(sd["a2c_network.sigma"]).detach().to("cpu", torch.float32).contiguous().numpy()
+            dst.append(_f32(sd[key]))
+    logstd = _f32(sd["a2c_network.sigma"]) if "a2c_network.sigma" in sd else None
     input_norm = None
     if "running_mean_std.running_mean" in sd or "running_mean_std.running_var" in sd:
         for key in ("running_mean_std.running_mean", "running_mean_std.running_var"):
             if key not in sd:
                 raise KeyError(f"rl_games checkpoint has no {key!r} next to the other half of running_mean_std")
-        mean = torch.as_tensor(sd["running_mean_std.running_mean"]).detach().to("cpu", torch.float32).numpy()
-        var = torch.as_tensor(sd["running_mean_std.running_var"]).detach().to("cpu", torch.float32).numpy()
+        mean, var = _f32(sd["running_mean_std.running_mean"]), _f32(sd["running_mean_std.running_var"])
         input_norm = (mean, np.sqrt(var + np.float32(NORM_EPSILON), dtype=np.float32), NORM_CLIP)
     return weights, biases, logstd, input_norm
 
 
-class ActorMLP:
-    """actor(obs) -> actions [N, A].  Build with from_arrays or from_rl_games_checkpoint."""
+class _Actor:
+    """What ActorMLP and RecurrentActor share: validation, the env-step count of the generator, the buffers kept per batch size,
+    the CPU statements of the normaliser and of sampling, and the library entries <_ENTRY>_{create, set_input_norm, set_logstd,
+    noise, destroy}.  A subclass sets obs_dim, action_dim and logstd (None: no constant log-std) before _setup."""
+    _ENTRY = None  # "agx_policy" / "agx_recurrent"
 
-    def __init__(self, weights, biases, logstd=None, activation="elu", input_norm=None, device="cuda:0", task=None, rng_seed=None,
-                 env_index_base=None):
-        if activation not in ACTIVATIONS:
-            raise ValueError(f"ActorMLP: activation {activation!r}; supported: 'none', 'elu', 'relu'")
-        self.activation = activation if activation is not None else "none"
-        self.weights = [np.ascontiguousarray(np.asarray(w, np.float32)) for w in weights]
-        self.biases = [np.ascontiguousarray(np.asarray(b, np.float32)) for b in biases]
-        if len(self.weights) != len(self.biases) or not self.weights:
-            raise ValueError(f"ActorMLP: {len(self.weights)} weights and {len(self.biases)} biases")
-        for l, (w, b) in enumerate(zip(self.weights, self.biases)):
+    @classmethod
+    def _check_layers(cls, weights, biases, what):
+        """(weights, biases, widths [in, out of layer 0, ...]) of a chain of Linear layers; `what` ("" or "encoder ") names them"""
+        name = cls.__name__
+        weights, biases = [_arr(w) for w in weights], [_arr(b) for b in biases]
+        if len(weights) != len(biases) or not weights:
+            raise ValueError(f"{name}: {len(weights)} {what}weights and {len(biases)} biases")
+        for l, (w, b) in enumerate(zip(weights, biases)):
             if w.ndim != 2 or b.shape != (w.shape[0],):
-                raise ValueError(f"ActorMLP: layer {l}: weight {w.shape} and bias {b.shape} are not [out, in] and [out]")
-            if l and w.shape[1] != self.weights[l - 1].shape[0]:
-                raise ValueError(f"ActorMLP: layer {l} reads {w.shape[1]} inputs, layer {l - 1} writes {self.weights[l - 1].shape[0]}")
-        self.dims = [self.weights[0].shape[1]] + [w.shape[0] for w in self.weights]
-        self.lds_bytes = check_dims(self.dims)
-        self.obs_dim, self.action_dim = self.dims[0], self.dims[-1]
-        self.logstd = None if logstd is None else np.ascontiguousarray(np.asarray(logstd, np.float32)).reshape(-1)
-        if self.logstd is not None and self.logstd.shape != (self.action_dim,):
-            raise ValueError(f"ActorMLP: logstd has {self.logstd.size} entries, the net has {self.action_dim} actions")
+                raise ValueError(f"{name}: {what}layer {l}: weight {w.shape} and bias {b.shape} are not [out, in] and [out]")
+            if l and w.shape[1] != weights[l - 1].shape[0]:
+                raise ValueError(f"{name}: {what}layer {l} reads {w.shape[1]} inputs, layer {l - 1} writes {weights[l - 1].shape[0]}")
+        return weights, biases, [weights[0].shape[1]] + [w.shape[0] for w in weights]
+
+    def _setup(self, input_norm, device, task, rng_seed, env_index_base):
         self.input_norm = None
         if input_norm is not None:
             mean, denom, clip = input_norm
-            mean = np.ascontiguousarray(np.asarray(mean, np.float32)).reshape(-1)
-            denom = np.ascontiguousarray(np.asarray(denom, np.float32)).reshape(-1)
+            mean, denom = _arr(mean).reshape(-1), _arr(denom).reshape(-1)
             if mean.shape != (self.obs_dim,) or denom.shape != (self.obs_dim,):
-                raise ValueError(f"ActorMLP: input_norm of widths {mean.size} / {denom.size}, the net reads {self.obs_dim} inputs")
+                raise ValueError(f"{type(self).__name__}: input_norm of widths {mean.size} / {denom.size}, the net reads {self.obs_dim} inputs")
             self.input_norm = (mean, denom, float(clip))
         self.device = str(device)
         self.task = task
@@ -129,28 +132,119 @@ class ActorMLP:
         self._out = {}
         self._handle = None
         self._is_cpu = torch.device(self.device).type == "cpu"
-        if self._is_cpu:
-            self._cpu = [(torch.from_numpy(w), torch.from_numpy(b)) for w, b in zip(self.weights, self.biases)]
-        else:
-            self._lib = _lib.load()
-            n = len(self.weights)
-            wp = (C.c_void_p * n)(*[w.ctypes.data for w in self.weights])
-            bp = (C.c_void_p * n)(*[b.ctypes.data for b in self.biases])
-            handle = C.c_void_p()
-            with torch.cuda.device(torch.device(self.device)):
-                _lib.check(self._lib.agx_policy_create(n, (C.c_int32 * len(self.dims))(*self.dims), wp, bp, ACTIVATIONS[self.activation],
-                                                       C.byref(handle)), "agx_policy_create")
-                self._handle = handle
-                if self.input_norm is not None:
-                    mean, denom, clip = self.input_norm
-                    _lib.check(self._lib.agx_policy_set_input_norm(handle, mean.ctypes.data, denom.ctypes.data, clip), "agx_policy_set_input_norm")
-                if self.logstd is not None:
-                    _lib.check(self._lib.agx_policy_set_logstd(handle, self.logstd.ctypes.data), "agx_policy_set_logstd")
+
+    def _create(self, *args):
+        """<_ENTRY>_create(*args, &handle) on this actor's device, then the normaliser and the constant log-std"""
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        with torch.cuda.device(torch.device(self.device)):
+            self._entry("create", *args, C.byref(handle))
+            self._handle = handle
+            if self.input_norm is not None:
+                mean, denom, clip = self.input_norm
+                self._entry("set_input_norm", handle, mean.ctypes.data, denom.ctypes.data, clip)
+            if self.logstd is not None:
+                self._entry("set_logstd", handle, self.logstd.ctypes.data)
+
+    def _entry(self, which, *args):
+        name = f"{self._ENTRY}_{which}"
+        _lib.check(getattr(self._lib, name)(*args), name)
 
     def __del__(self):
         handle, self._handle = getattr(self, "_handle", None), None
         if handle:
-            self._lib.agx_policy_destroy(handle)
+            getattr(self._lib, f"{self._ENTRY}_destroy")(handle)
+
+    def _check_obs(self, obs):
+        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype is not torch.float32:
+            raise ValueError(f"{type(self).__name__}: observations must be float32 [N, {self.obs_dim}], got {obs.dtype} {tuple(obs.shape)}")
+        return obs.shape[0]
+
+    def _check_eps(self, eps, n):
+        if eps is not None and (tuple(eps.shape) != (n, self.action_dim) or eps.dtype is not torch.float32):
+            raise ValueError(f"{type(self).__name__}: eps must be float32 [{n}, {self.action_dim}]")
+
+    def _buffers(self, n, count):
+        """`count` tensors [n, action_dim] kept per batch size: the actions without out=, the mean (and the log-std)"""
+        bufs = self._out.get(n)
+        if bufs is None:
+            bufs = self._out[n] = tuple(torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device) for _ in range(count))
+        return bufs
+
+    def _check_out(self, out, buf, n):
+        """out= when given, else the kept buffer"""
+        if out is None:
+            return buf
+        if tuple(out.shape) != (n, self.action_dim) or out.dtype is not torch.float32:
+            raise ValueError(f"{type(self).__name__}: out must be float32 [{n}, {self.action_dim}]")
+        return out
+
+    def _env_step(self, step, sample):
+        if step is not None:
+            return int(step)
+        env = getattr(self.task, "sim_env", None)
+        if env is not None:
+            return int(env.step_counter)
+        s = self.step
+        if sample:
+            self.step += 1
+        return s
+
+    @staticmethod
+    def _flag_word(sample, clamp):
+        return (_lib.POLICY_SAMPLE if sample else 0) | (_lib.POLICY_CLAMP if clamp else 0)
+
+    def _normalise_cpu(self, x):
+        if self.input_norm is None:
+            return x
+        m, d, clip = self.input_norm
+        return torch.clamp((x - torch.from_numpy(m)) / torch.from_numpy(d), -clip, clip)
+
+    def _emit_cpu(self, mean, logstd, out, sample, clamp, eps):
+        """out <- mean -> (sample with sigma = exp(logstd)) -> (clamp)"""
+        a = mean
+        if sample:
+            if eps is None:
+                raise ValueError(f"{type(self).__name__} on a CPU device has no generator: pass eps= to sample")
+            a = mean + eps * torch.exp(logstd)
+        if clamp:
+            a = a.clamp(-1.0, 1.0)
+        out.copy_(a)
+
+    def noise(self, n, step):
+        """[n, action_dim]: the normals a sampled call without eps draws at env step `step` (diagnostic; one stream for both actors)"""
+        if self._is_cpu:
+            raise RuntimeError(f"{type(self).__name__}.noise: the generator lives in the HIP library; this actor is on a CPU device")
+        out = torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device)
+        self._entry("noise", self._handle, n, self.rng_seed, self.env_index_base, int(step) & 0x7FFFFFFF, _lib.dptr(out), _lib.current_stream(self.device))
+        return out
+
+
+def _pointers(arrays):
+    return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+class ActorMLP(_Actor):
+    """actor(obs) -> actions [N, A].  Build with from_arrays or from_rl_games_checkpoint."""
+    _ENTRY = "agx_policy"
+
+    def __init__(self, weights, biases, logstd=None, activation="elu", input_norm=None, device="cuda:0", task=None, rng_seed=None,
+                 env_index_base=None):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"ActorMLP: activation {activation!r}; supported: 'none', 'elu', 'relu'")
+        self.activation = activation if activation is not None else "none"
+        self.weights, self.biases, self.dims = self._check_layers(weights, biases, "")
+        self.lds_bytes = check_dims(self.dims)
+        self.obs_dim, self.action_dim = self.dims[0], self.dims[-1]
+        self.logstd = None if logstd is None else _arr(logstd).reshape(-1)
+        if self.logstd is not None and self.logstd.shape != (self.action_dim,):
+            raise ValueError(f"ActorMLP: logstd has {self.logstd.size} entries, the net has {self.action_dim} actions")
+        self._setup(input_norm, device, task, rng_seed, env_index_base)
+        if self._is_cpu:
+            self._cpu = [(torch.from_numpy(w), torch.from_numpy(b)) for w, b in zip(self.weights, self.biases)]
+        else:
+            self._create(len(self.weights), (C.c_int32 * len(self.dims))(*self.dims), _pointers(self.weights), _pointers(self.biases),
+                         ACTIVATIONS[self.activation])
 
     # ---- constructors ----------------------------------------------------------------------------------------------------
     @classmethod
@@ -174,58 +268,31 @@ class ActorMLP:
                         device=device, task=self.task, rng_seed=self.rng_seed, env_index_base=self.env_index_base)
 
     # ---- the call --------------------------------------------------------------------------------------------------------
-    def _buffers(self, n):
-        bufs = self._out.get(n)
-        if bufs is None:
-            bufs = self._out[n] = (torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device),
-                                   torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device))
-        return bufs
-
-    def _env_step(self, step, sample):
-        if step is not None:
-            return int(step)
-        env = getattr(self.task, "sim_env", None)
-        if env is not None:
-            return int(env.step_counter)
-        s = self.step
-        if sample:
-            self.step += 1
-        return s
-
     def __call__(self, obs, out=None, sample=False, clamp=False, eps=None, step=None):
         """obs [N, obs_dim] float32 -> actions [N, action_dim]; `actor.mean` then holds the mean of this call.  sample: a = mu +
         eps * exp(logstd), eps given ([N, action_dim]) or drawn by the library's generator at (rng_seed, env_index_base + env,
         step, action) -- step: the task's env step, or this object's own count of sampled calls.  clamp: to [-1, 1], last.
         Without out= the result lives in a buffer kept per batch size: the next call of that size overwrites it."""
-        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype is not torch.float32:
-            raise ValueError(f"ActorMLP: observations must be float32 [N, {self.obs_dim}], got {obs.dtype} {tuple(obs.shape)}")
-        n = obs.shape[0]
+        n = self._check_obs(obs)
         if sample and self.logstd is None:
             raise ValueError("ActorMLP: sample=True needs a logstd (the checkpoint's a2c_network.sigma)")
-        if eps is not None and (tuple(eps.shape) != (n, self.action_dim) or eps.dtype is not torch.float32):
-            raise ValueError(f"ActorMLP: eps must be float32 [{n}, {self.action_dim}]")
-        buf, mean = self._buffers(n)
-        if out is None:
-            out = buf
-        elif tuple(out.shape) != (n, self.action_dim) or out.dtype is not torch.float32:
-            raise ValueError(f"ActorMLP: out must be float32 [{n}, {self.action_dim}]")
+        self._check_eps(eps, n)
+        buf, mean = self._buffers(n, 2)
+        out = self._check_out(out, buf, n)
         env_step = self._env_step(step, sample and eps is None)
         if self._is_cpu:
             return self._call_cpu(obs, out, mean, sample, clamp, eps)
         if not obs.is_contiguous():
             obs = obs.contiguous()
-        flags = (_lib.POLICY_SAMPLE if sample else 0) | (_lib.POLICY_CLAMP if clamp else 0)
         p = _lib.dptr
-        _lib.check(self._lib.agx_policy_act(self._handle, n, p(obs), p(out), p(mean), p(eps) if sample else None, flags, self.rng_seed,
-                                            self.env_index_base, env_step & 0x7FFFFFFF, _lib.current_stream(self.device)), "agx_policy_act")
+        _lib.check(self._lib.agx_policy_act(self._handle, n, p(obs), p(out), p(mean), p(eps) if sample else None, self._flag_word(sample, clamp),
+                                            self.rng_seed, self.env_index_base, env_step & 0x7FFFFFFF, _lib.current_stream(self.device)),
+                   "agx_policy_act")
         self.mean = mean
         return out
 
     def _call_cpu(self, obs, out, mean, sample, clamp, eps):
-        x = obs
-        if self.input_norm is not None:
-            m, d, clip = self.input_norm
-            x = torch.clamp((x - torch.from_numpy(m)) / torch.from_numpy(d), -clip, clip)
+        x = self._normalise_cpu(obs)
         last = len(self._cpu) - 1
         for l, (w, b) in enumerate(self._cpu):
             x = torch.nn.functional.linear(x, w, b)
@@ -235,23 +302,8 @@ class ActorMLP:
                 elif self.activation == "relu":
                     x = torch.relu(x)
         mean.copy_(x)
-        if sample:
-            if eps is None:
-                raise ValueError("ActorMLP on a CPU device has no generator: pass eps= to sample")
-            x = x + eps * torch.exp(torch.from_numpy(self.logstd))
-        if clamp:
-            x = x.clamp(-1.0, 1.0)
-        out.copy_(x)
+        self._emit_cpu(mean, torch.from_numpy(self.logstd) if sample else None, out, sample, clamp, eps)
         self.mean = mean
-        return out
-
-    def noise(self, n, step):
-        """[n, action_dim]: the normals a sampled call without eps draws at env step `step` (diagnostic)"""
-        if self._is_cpu:
-            raise RuntimeError("ActorMLP.noise: the generator lives in the HIP library; this actor is on a CPU device")
-        out = torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.agx_policy_noise(self._handle, n, self.rng_seed, self.env_index_base, int(step) & 0x7FFFFFFF, _lib.dptr(out),
-                                              _lib.current_stream(self.device)), "agx_policy_noise")
         return out
 
 
@@ -275,10 +327,6 @@ def check_recurrent_dims(dims, hidden, head_out):
     if lib.agx_recurrent_check(len(dims) - 1, (C.c_int32 * len(dims))(*dims), int(hidden), int(head_out), C.byref(lds)) != 0:
         raise ValueError(lib.agx_last_error().decode("utf-8", "replace"))
     return int(lds.value)
-
-
-def _f32(t):
-    return np.ascontiguousarray(torch.as_tensor(t).detach().to("cpu", torch.float32).contiguous().numpy())
 
 
 def recurrent_arrays_from_state_dict(sd):
@@ -374,27 +422,19 @@ def find_sample_factory_checkpoint(path_or_dir, kind="best"):
     return found[-1]
 
 
-class RecurrentActor:
+class RecurrentActor(_Actor):
     """actor(obs, done) -> actions [N, A] of an encoder MLP -> GRU cell -> linear head; the state lives in `actor.hidden` [N, H].
     Build with from_arrays or from_sample_factory_checkpoint."""
+    _ENTRY = "agx_recurrent"
 
     def __init__(self, enc_weights, enc_biases, w_ih, w_hh, b_ih, b_hh, head_weight, head_bias, logstd=None, activation="elu", input_norm=None,
                  device="cuda:0", task=None, rng_seed=None, env_index_base=None):
         if activation not in ("elu", "relu"):
             raise ValueError(f"RecurrentActor: activation {activation!r}; supported: 'elu', 'relu'")
         self.activation = activation
-        arr = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))  # noqa: E731
-        self.enc_weights, self.enc_biases = [arr(w) for w in enc_weights], [arr(b) for b in enc_biases]
-        if len(self.enc_weights) != len(self.enc_biases) or not self.enc_weights:
-            raise ValueError(f"RecurrentActor: {len(self.enc_weights)} encoder weights and {len(self.enc_biases)} biases")
-        for l, (w, b) in enumerate(zip(self.enc_weights, self.enc_biases)):
-            if w.ndim != 2 or b.shape != (w.shape[0],):
-                raise ValueError(f"RecurrentActor: encoder layer {l}: weight {w.shape} and bias {b.shape} are not [out, in] and [out]")
-            if l and w.shape[1] != self.enc_weights[l - 1].shape[0]:
-                raise ValueError(f"RecurrentActor: encoder layer {l} reads {w.shape[1]} inputs, layer {l - 1} writes {self.enc_weights[l - 1].shape[0]}")
-        self.dims = [self.enc_weights[0].shape[1]] + [w.shape[0] for w in self.enc_weights]
-        self.w_ih, self.w_hh, self.b_ih, self.b_hh = arr(w_ih), arr(w_hh), arr(b_ih).reshape(-1), arr(b_hh).reshape(-1)
-        self.head_weight, self.head_bias = arr(head_weight), arr(head_bias).reshape(-1)
+        self.enc_weights, self.enc_biases, self.dims = self._check_layers(enc_weights, enc_biases, "encoder ")
+        self.w_ih, self.w_hh, self.b_ih, self.b_hh = _arr(w_ih), _arr(w_hh), _arr(b_ih).reshape(-1), _arr(b_hh).reshape(-1)
+        self.head_weight, self.head_bias = _arr(head_weight), _arr(head_bias).reshape(-1)
         if self.w_hh.ndim != 2 or self.w_hh.shape[0] != 3 * self.w_hh.shape[1]:
             raise ValueError(f"RecurrentActor: w_hh {self.w_hh.shape} is not [3 H, H] (a GRU, gates r, z, n)")
         self.hidden_dim = H = self.w_hh.shape[1]
@@ -404,7 +444,7 @@ class RecurrentActor:
         if self.head_weight.ndim != 2 or self.head_weight.shape[1] != H or self.head_bias.shape != (self.head_weight.shape[0],):
             raise ValueError(f"RecurrentActor: head weight {self.head_weight.shape} and bias {self.head_bias.shape} do not read {H} inputs")
         P = self.head_weight.shape[0]
-        self.logstd = None if logstd is None else arr(logstd).reshape(-1)
+        self.logstd = None if logstd is None else _arr(logstd).reshape(-1)
         self.adaptive = self.logstd is None
         if self.adaptive and P % 2:
             raise ValueError(f"RecurrentActor: an adaptive head emits means and log-std: {P} outputs is odd (pass logstd= for a constant one)")
@@ -415,51 +455,18 @@ class RecurrentActor:
             raise ValueError(f"RecurrentActor: {self.action_dim} actions; supported: 1 .. 64")
         self.obs_dim = self.dims[0]
         self.lds_bytes = check_recurrent_dims(self.dims, H, P)
-        self.input_norm = None
-        if input_norm is not None:
-            mean, denom, clip = input_norm
-            mean, denom = arr(mean).reshape(-1), arr(denom).reshape(-1)
-            if mean.shape != (self.obs_dim,) or denom.shape != (self.obs_dim,):
-                raise ValueError(f"RecurrentActor: input_norm of widths {mean.size} / {denom.size}, the net reads {self.obs_dim} inputs")
-            self.input_norm = (mean, denom, float(clip))
-        self.device = str(device)
-        self.task = task
-        env = getattr(task, "sim_env", None)
-        self.rng_seed = int(rng_seed if rng_seed is not None else getattr(env, "rng_seed", 0)) & 0xFFFFFFFFFFFFFFFF
-        self.env_index_base = int(env_index_base if env_index_base is not None else getattr(env, "env_offset", 0))
-        self.step = 0
+        self._setup(input_norm, device, task, rng_seed, env_index_base)
         self.hidden = None  # [N, H], allocated by the first call
-        self.mean = self.logstd_out = None
+        self.logstd_out = None
         self._may_resize = True
-        self._out = {}
-        self._handle = None
-        self._is_cpu = torch.device(self.device).type == "cpu"
         if self._is_cpu:
             t = torch.from_numpy
             self._cpu = {"enc": [(t(w), t(b)) for w, b in zip(self.enc_weights, self.enc_biases)], "ih": (t(self.w_ih), t(self.b_ih)),
                          "hh": (t(self.w_hh), t(self.b_hh)), "head": (t(self.head_weight), t(self.head_bias))}
         else:
-            self._lib = _lib.load()
-            n = len(self.enc_weights)
-            wp = (C.c_void_p * n)(*[w.ctypes.data for w in self.enc_weights])
-            bp = (C.c_void_p * n)(*[b.ctypes.data for b in self.enc_biases])
-            handle = C.c_void_p()
-            with torch.cuda.device(torch.device(self.device)):
-                _lib.check(self._lib.agx_recurrent_create(n, (C.c_int32 * len(self.dims))(*self.dims), H, self.action_dim, int(self.adaptive), wp, bp,
-                                                          self.w_ih.ctypes.data, self.w_hh.ctypes.data, self.b_ih.ctypes.data, self.b_hh.ctypes.data,
-                                                          self.head_weight.ctypes.data, self.head_bias.ctypes.data, ACTIVATIONS[activation],
-                                                          C.byref(handle)), "agx_recurrent_create")
-                self._handle = handle
-                if self.input_norm is not None:
-                    mean, denom, clip = self.input_norm
-                    _lib.check(self._lib.agx_recurrent_set_input_norm(handle, mean.ctypes.data, denom.ctypes.data, clip), "agx_recurrent_set_input_norm")
-                if not self.adaptive:
-                    _lib.check(self._lib.agx_recurrent_set_logstd(handle, self.logstd.ctypes.data), "agx_recurrent_set_logstd")
-
-    def __del__(self):
-        handle, self._handle = getattr(self, "_handle", None), None
-        if handle:
-            self._lib.agx_recurrent_destroy(handle)
+            self._create(len(self.enc_weights), (C.c_int32 * len(self.dims))(*self.dims), H, self.action_dim, int(self.adaptive),
+                         _pointers(self.enc_weights), _pointers(self.enc_biases), self.w_ih.ctypes.data, self.w_hh.ctypes.data, self.b_ih.ctypes.data,
+                         self.b_hh.ctypes.data, self.head_weight.ctypes.data, self.head_bias.ctypes.data, ACTIVATIONS[activation])
 
     # ---- constructors ----------------------------------------------------------------------------------------------------
     @classmethod
@@ -517,14 +524,6 @@ class RecurrentActor:
             self.hidden[env_ids] = 0.0
 
     # ---- the call --------------------------------------------------------------------------------------------------------
-    def _buffers(self, n):
-        bufs = self._out.get(n)
-        if bufs is None:
-            bufs = self._out[n] = tuple(torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device) for _ in range(3))
-        return bufs
-
-    _env_step = ActorMLP._env_step
-
     def __call__(self, obs, done=None, reset="before", out=None, sample=False, clamp=False, eps=None, step=None):
         """obs [N, obs_dim] float32 -> actions [N, action_dim]; `actor.hidden` advances in place, `actor.mean` and
         `actor.logstd_out` then hold this call's values.  done: None, one bool / uint8 tensor [N] or a tuple of two (an env with
@@ -532,13 +531,10 @@ class RecurrentActor:
         evaluated from a zero state (sample-factory's sampler, with the flags of the step that produced obs); "after": it is
         evaluated with the state it has, and zero is stored (the reference's dce_nn_navigation.py).  sample / clamp / eps / step
         / out as for ActorMLP; sigma = exp(logstd) of the head."""
-        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype is not torch.float32:
-            raise ValueError(f"RecurrentActor: observations must be float32 [N, {self.obs_dim}], got {obs.dtype} {tuple(obs.shape)}")
+        n = self._check_obs(obs)
         if reset not in ("before", "after"):
             raise ValueError(f"RecurrentActor: reset {reset!r}; supported: 'before', 'after'")
-        n = obs.shape[0]
-        if eps is not None and (tuple(eps.shape) != (n, self.action_dim) or eps.dtype is not torch.float32):
-            raise ValueError(f"RecurrentActor: eps must be float32 [{n}, {self.action_dim}]")
+        self._check_eps(eps, n)
         if sample and eps is None and self._is_cpu:  # refused before the step count or the state moves
             raise ValueError("RecurrentActor on a CPU device has no generator: pass eps= to sample")
         flags = () if done is None else (tuple(done) if isinstance(done, (tuple, list)) else (done,))
@@ -552,17 +548,14 @@ class RecurrentActor:
         elif self.hidden.shape[0] != n:
             raise ValueError(f"RecurrentActor: {n} envs, the state holds {self.hidden.shape[0]}: call reset() before changing the batch size")
         self._may_resize = False
-        buf, mean, logstd_out = self._buffers(n)
-        if out is None:
-            out = buf
-        elif tuple(out.shape) != (n, self.action_dim) or out.dtype is not torch.float32:
-            raise ValueError(f"RecurrentActor: out must be float32 [{n}, {self.action_dim}]")
+        buf, mean, logstd_out = self._buffers(n, 3)
+        out = self._check_out(out, buf, n)
         env_step = self._env_step(step, sample and eps is None)
         if self._is_cpu:
             return self._call_cpu(obs, flags, reset, out, mean, logstd_out, sample, clamp, eps)
         if not obs.is_contiguous():
             obs = obs.contiguous()
-        bits = (_lib.POLICY_SAMPLE if sample else 0) | (_lib.POLICY_CLAMP if clamp else 0) | (_lib.POLICY_RESET_AFTER if reset == "after" else 0)
+        bits = self._flag_word(sample, clamp) | (_lib.POLICY_RESET_AFTER if reset == "after" else 0)
         p = _lib.dptr
         _lib.check(self._lib.agx_recurrent_act(self._handle, n, p(obs), p(self.hidden), p(flags[0]) if flags else None,
                                                p(flags[1]) if len(flags) > 1 else None, p(out), p(mean), p(logstd_out), p(eps) if sample else None,
@@ -573,10 +566,7 @@ class RecurrentActor:
 
     def _call_cpu(self, obs, flags, reset, out, mean, logstd_out, sample, clamp, eps):
         F = torch.nn.functional
-        x = obs
-        if self.input_norm is not None:
-            m, d, clip = self.input_norm
-            x = torch.clamp((x - torch.from_numpy(m)) / torch.from_numpy(d), -clip, clip)
+        x = self._normalise_cpu(obs)
         for w, b in self._cpu["enc"]:
             x = F.linear(x, w, b)
             x = F.elu(x) if self.activation == "elu" else torch.relu(x)
@@ -597,22 +587,8 @@ class RecurrentActor:
         A = self.action_dim
         mean.copy_(y[:, :A])
         logstd_out.copy_(y[:, A:] if self.adaptive else torch.from_numpy(self.logstd).expand_as(mean))
-        a = mean
-        if sample:
-            a = mean + eps * torch.exp(logstd_out)
-        if clamp:
-            a = a.clamp(-1.0, 1.0)
-        out.copy_(a)
+        self._emit_cpu(mean, logstd_out, out, sample, clamp, eps)
         self.mean, self.logstd_out = mean, logstd_out
-        return out
-
-    def noise(self, n, step):
-        """[n, action_dim]: the normals a sampled call without eps draws at env step `step` (the stream of ActorMLP.noise)"""
-        if self._is_cpu:
-            raise RuntimeError("RecurrentActor.noise: the generator lives in the HIP library; this actor is on a CPU device")
-        out = torch.empty((n, self.action_dim), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.agx_recurrent_noise(self._handle, n, self.rng_seed, self.env_index_base, int(step) & 0x7FFFFFFF, _lib.dptr(out),
-                                                 _lib.current_stream(self.device)), "agx_recurrent_noise")
         return out
 
 

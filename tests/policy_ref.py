@@ -42,20 +42,26 @@ def act64(x, activation):
     return x
 
 
+def linear64(x, err, w, b):
+    """y = W x + b in float64 from float32 operands, and the bound of a float32 evaluation in ANY summation order:
+    E_y = |W| E_x + (K + 2) u (|W| (|x| + E_x) + |b|) -- the incoming error through |W|, K + 2 rounded additions of partial sums no
+    larger than the magnitude sum"""
+    w64, b64 = torch.as_tensor(w).double(), torch.as_tensor(b).double()
+    y = F.linear(x, w64, b64)
+    mag = F.linear(x.abs() + err, w64.abs(), b64.abs())
+    return y, F.linear(err, w64.abs()) + (w64.shape[1] + 2) * U * mag
+
+
 def mlp64(ws, bs, x, activation):
     """the net in float64 from float32 operands, end to end: (mean [N, out], bound [N, out], pre-activations per layer).
-    bound: E_0 = 0, E_l = |W_l| E_{l-1} + (K_l + 2) u (|W_l| (|x_{l-1}| + E_{l-1}) + |b_l|) + u |y_l| -- the error a float32
-    evaluation in ANY summation order can have: the incoming error through |W|, K + 2 rounded additions of partial sums no larger
-    than the magnitude sum, the activation a contraction followed by one rounding."""
+    bound: E_0 = 0, E_l = linear64's bound + u |y_l|: the activation is a contraction followed by one rounding."""
     x = torch.as_tensor(x).double()
     err = torch.zeros_like(x)
     pres = []
     for l, (w, b) in enumerate(zip(ws, bs)):
-        w64, b64 = torch.as_tensor(w).double(), torch.as_tensor(b).double()
-        pre = F.linear(x, w64, b64)
-        mag = F.linear(x.abs() + err, w64.abs(), b64.abs())
+        pre, err = linear64(x, err, w, b)
         y = act64(pre, activation) if l + 1 < len(ws) else pre
-        err = F.linear(err, w64.abs()) + (w64.shape[1] + 2) * U * mag + U * y.abs()
+        err = err + U * y.abs()
         pres.append(pre)
         x = y
     return x, err, pres

@@ -8,7 +8,7 @@ r, z, n), head_weight [P][H], head_bias [P], logstd (None: the head is adaptive,
 activation ("elu" / "relu").
 
 The bound (step64).  u = 2^-24.  E_v is a bound on |float32 value - float64 value| of v.
-  linear map y = W x + b with K inputs, as policy_ref.mlp64:  E_y = |W| E_x + (K + 2) u (|W| (|x| + E_x) + |b|): the incoming
+  linear map y = W x + b with K inputs (policy_ref.linear64):  E_y = |W| E_x + (K + 2) u (|W| (|x| + E_x) + |b|): the incoming
     error through |W|, and K + 2 rounded additions of partial sums no larger than the magnitude sum, in ANY summation order.
   a rounded operation (+, -, *) adds u times the magnitude of its result; a product p = a b carries |a| E_b + |b| E_a + E_a E_b.
   an elementary function f with Lipschitz constant c adds c E_in + fn u |f|: c = 1 for ELU / ReLU and tanh, 1/4 for the sigmoid.
@@ -32,18 +32,12 @@ import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
+from policy_ref import U, act64, bits, linear64, norm_f32, sample_f32  # noqa: F401  (the shared statements; tests take them from here too)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURE = os.path.join(GOLDEN, "policy_lmf2_nav_recurrent_actor.npz")
-U = 2.0 ** -24  # unit roundoff of float32
 FN_TORCH = 4.0  # units of roundoff one of torch's float32 CPU elementary functions may add (docstring); the device's add 1
 SF_EPSILON, SF_CLIP = 1e-5, 5.0
-
-
-def bits(a):
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def sf_denom(var):
@@ -100,17 +94,6 @@ def num_actions(net):
 
 
 # ---- float64 with the bound ------------------------------------------------------------------------------------------------------
-def _linear64(x, err, w, b):
-    w64, b64 = torch.as_tensor(w).double(), torch.as_tensor(b).double()
-    y = F.linear(x, w64, b64)
-    mag = F.linear(x.abs() + err, w64.abs(), b64.abs())
-    return y, F.linear(err, w64.abs()) + (w64.shape[1] + 2) * U * mag
-
-
-def _act64(x, activation):
-    return torch.where(x > 0, x, torch.expm1(x)) if activation == "elu" else torch.where(x < 0, torch.zeros_like(x), x)
-
-
 def step64(net, obs, h, err_h, flagged=None, reset="before", fn=1.0):
     """one call in float64 from float32 operands.  obs [N, in] float32, h [N, H] float64 (the stored state), err_h its bound,
     flagged: bool [N] or None.  Returns a dict of float64 tensors: mean, logstd, hidden (what is stored), and the bounds err_mean,
@@ -126,8 +109,8 @@ def step64(net, obs, h, err_h, flagged=None, reset="before", fn=1.0):
         err = torch.where(v.abs() - err >= clip, torch.zeros_like(err), err)  # beyond the clip in both precisions: exact
         x = v.clamp(-clip, clip)
     for w, b in zip(net["enc_weights"], net["enc_biases"]):
-        pre, err = _linear64(x, err, w, b)
-        x = _act64(pre, net["activation"])
+        pre, err = linear64(x, err, w, b)
+        x = act64(pre, net["activation"])
         err = err + fn * U * x.abs()
     h = torch.as_tensor(h).double()
     err_h = torch.as_tensor(err_h).double()
@@ -135,8 +118,8 @@ def step64(net, obs, h, err_h, flagged=None, reset="before", fn=1.0):
         h = torch.where(flagged[:, None], torch.zeros_like(h), h)
         err_h = torch.where(flagged[:, None], torch.zeros_like(err_h), err_h)
     H = h.shape[1]
-    gi, e_gi = _linear64(x, err, net["w_ih"], net["b_ih"])
-    gh, e_gh = _linear64(h, err_h, net["w_hh"], net["b_hh"])
+    gi, e_gi = linear64(x, err, net["w_ih"], net["b_ih"])
+    gh, e_gh = linear64(h, err_h, net["w_hh"], net["b_hh"])
     s = gi[:, :2 * H] + gh[:, :2 * H]
     e_s = e_gi[:, :2 * H] + e_gh[:, :2 * H] + U * s.abs()
     rz = torch.sigmoid(s)
@@ -157,7 +140,7 @@ def step64(net, obs, h, err_h, flagged=None, reset="before", fn=1.0):
     e_c = z.abs() * err_h + h.abs() * e_z + e_z * err_h + U * c.abs()
     hn = b + c
     e_hn = e_b + e_c + U * hn.abs()
-    y, e_y = _linear64(hn, e_hn, net["head_weight"], net["head_bias"])
+    y, e_y = linear64(hn, e_hn, net["head_weight"], net["head_bias"])
     A = num_actions(net)
     stored, e_stored = hn, e_hn
     if flagged is not None and reset == "after":
@@ -195,21 +178,6 @@ def gates_f32(gi, gh, h, sigmoid=sigmoid_f32, tanh=tanh_f32):
     b = (a * n).astype(np.float32)
     c = (z * h).astype(np.float32)
     return (b + c).astype(np.float32)
-
-
-def norm_f32(x, mean, denom, clip):
-    x, mean, denom = np.asarray(x, np.float32), np.asarray(mean, np.float32), np.asarray(denom, np.float32)
-    v = ((x - mean).astype(np.float32) / denom).astype(np.float32)
-    return np.clip(v, np.float32(-clip), np.float32(clip)).astype(np.float32)
-
-
-def sample_f32(mu, eps, logstd, clamp=False):
-    """a = mu + eps * exp(logstd) in numpy float32, every operation rounded: exp in float64 rounded once"""
-    mu, eps = np.asarray(mu, np.float32), np.asarray(eps, np.float32)
-    sigma = np.exp(np.asarray(logstd, np.float32).astype(np.float64)).astype(np.float32)
-    t = (eps * sigma).astype(np.float32)
-    a = (mu + t).astype(np.float32)
-    return np.clip(a, np.float32(-1.0), np.float32(1.0)) if clamp else a
 
 
 # ---- torch's own GRU on the same weights ----------------------------------------------------------------------------------------

@@ -105,6 +105,23 @@ def test_fused_equals_the_layer_chain_bit_for_bit(name):
                 assert np.array_equal(bits(actor.mean), bits(want))
 
 
+def test_a_smaller_actor_created_later_does_not_disturb_a_larger_one():
+    """131072 bytes of LDS, then an actor of 73728 bytes (both above 64 KiB: the kernel's dynamic-LDS attribute matters to both),
+    then the small one and the large one are called: the twin of the test of that name in test_gpu_recurrent_policy.py.  Measured
+    (MI355X, ROCm 7.2): also passes when create sets the attribute to the actor's own size, as it did before it set the limit"""
+    (big_ws, big_bs), (small_ws, small_bs) = _net("15-512-512-4"), _net("in-512")
+    big = _actor(big_ws, big_bs)
+    small = _actor(small_ws, small_bs)
+    assert big.lds_bytes == 131072 and small.lds_bytes == 73728
+    g = _gen(8)
+    obs = (torch.rand((33, 15), generator=g) * 4 - 2).to(DEV)
+    small((torch.rand((33, 512), generator=g) * 4 - 2).to(DEV))
+    got = big(obs)
+    want = Chain(big_ws, big_bs)(obs, "elu")
+    torch.cuda.synchronize()
+    assert torch.isfinite(want).all() and np.array_equal(bits(got), bits(want))
+
+
 @pytest.mark.parametrize("n", [1, 33, 129])
 def test_exact_inputs_equal_float64_bit_for_bit(n):
     """13 -> 32 -> 4, ReLU; weights and biases on the 1/8 grid, inputs on the 1/16 grid, all in [-1, 1].  Layer 1: products are
