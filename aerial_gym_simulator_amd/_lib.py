@@ -298,6 +298,16 @@ class AgxComOffset(C.Structure):
     _fields_ = [("c", C.c_float * 3), ("reserved", C.c_float)]
 
 
+ROLLOUT_MAX_CHANNELS = 32  # AGX_ROLLOUT_MAX_CHANNELS
+REC_STATE, REC_DERIVED, REC_THRUST, REC_CRASH = 0, 1, 2, 3  # AGX_REC_*
+
+
+class AgxRolloutRecord(C.Structure):
+    """what agx_env_rollout stores after every step: out [steps][channels][N], one (source, component) per channel"""
+    _fields_ = [("out", C.c_void_p), ("channels", C.c_int32), ("reserved", C.c_int32),
+                ("source", C.c_int32 * ROLLOUT_MAX_CHANNELS), ("component", C.c_int32 * ROLLOUT_MAX_CHANNELS)]
+
+
 class AgxVaeConv(C.Structure):
     """one convolution of the VAE encoder (agx_vae_conv2d)"""
     _fields_ = [(k, C.c_int32) for k in ("cin", "cout", "kh", "kw", "stride", "pad_h", "pad_w", "in_h", "in_w", "out_h", "out_w",
@@ -337,6 +347,8 @@ _SIGNATURES = {
     "agx_env_step": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, C.POINTER(AgxTaskArgs), _P]),
     "agx_env_step_com": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, C.POINTER(AgxTaskArgs),
                                    C.POINTER(AgxComOffset), _P]),
+    "agx_env_rollout": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, C.c_int, C.c_int, C.c_int, _P,
+                                  C.POINTER(AgxRolloutRecord), _P, _P]),
     "agx_update_states": (C.c_int, [C.POINTER(AgxEnvBuffers), C.c_int, _P]),
     "agx_collide_spheres_boxes": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P]),
     "agx_controller_wrench": (C.c_int, [C.POINTER(AgxRobotParams), C.POINTER(AgxEnvBuffers), C.c_int, _P, _P]),

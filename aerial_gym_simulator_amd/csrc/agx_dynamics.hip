@@ -320,6 +320,9 @@ extern "C" int agx_env_step_com(const AgxRobotParams *P, const AgxEnvBuffers *B,
   return env_step("agx_env_step_com", P, B, n, actions_in, k, task, com, stream);
 }
 
+// T task-free env steps in one launch (k_env_step_rollout, agx_env_rollout): uses check_common, pick_block and the LDS bounds above
+#include "agx_dyn_rollout.h"
+
 extern "C" int agx_env_step_kernel(const AgxRobotParams *P, const AgxEnvBuffers *B, int n, int k, const AgxTaskArgs *task, char *out,
                                    int cap) {
   AGX_REQUIRE(P && B && out && cap > 0 && n > 0, "bad arguments");

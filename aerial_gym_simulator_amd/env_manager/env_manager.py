@@ -825,6 +825,20 @@ class EnvManager(BaseManager):
             self._buffers.push_wait_seq = 0  # the env-step kernel has waited for the row slot; the kernels behind it need not
         self._end_step()
 
+    @roctx.ranged("EnvManager.rollout")
+    def rollout(self, actions, steps=None, record=(), out=None):
+        """T env steps under known actions as ONE launch (rollout.py, agx_env_rollout): the simulator ends exactly where
+        `for t in range(T): self.step(actions_t)` leaves it, bit for bit -- dict tensors, step counter, flag parity, python's
+        `random` stream, the device-generator streams.  actions: float32 [N, A] held for `steps` steps, or [T, N, A], one block
+        per step.  record: keys of rollout.RECORD_KEYS; `rec[key]` is a [T, N, C] view of what the dict's tensor held after
+        every step, `rec.first_crash_step` int32 [N] the first step an env's crash flag was set (or -1; a crashed env keeps
+        flying, as in the loop).  out: the RolloutRecord of an earlier call of the same shape and keys, reused in place.
+        Raw EnvManager only: a task-owned env, user controller / robot classes, env_actions, strict_rng with disturbance, an
+        IMU, lean_step, step_graph, exchange rows, ROVs and off-centre masses are refused by name."""
+        from ..rollout import rollout
+
+        return rollout(self, actions, steps, record, out)
+
     def compute_observations(self):
         """env_manager.py:358-362: collision_tensor |= contact.  The fused step (step / simulate) has already accumulated the flag
         over its sub-step positions; this is the stand-alone form for callers that drive simulate() and compute_observations()

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define AGX_ABI_VERSION 25
+#define AGX_ABI_VERSION 25  /* (agx_env_rollout / AgxRolloutRecord were ADDED under 25: a new symbol and a new struct, no existing
+                               layout or signature changed, so a caller built against the earlier 25 header keeps working) */
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -310,6 +311,43 @@ typedef struct AgxComOffset {
 } AgxComOffset;
 int agx_env_step_com(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs, const float *actions_in, int k_substeps,
                      const AgxTaskArgs *task, const AgxComOffset *com, void *stream);
+
+/* Open-loop rollout: `steps` env steps of the task-free multirotor step in ONE launch (k_env_step_rollout<M, CTRL, WIDE>), in place
+ * of the reference's one-call-per-step loops under known actions -- EnvManager.step (env_manager.py:399-432) driven `steps`
+ * times, as examples/sys_id.py:56-90 does 500 times per action axis with a host copy of one dict tensor after every step.
+ * The buffers end where `steps` calls agx_env_step(params, buf, n, actions_t, k_t, NULL, stream) leave them, bit for bit, with
+ * buf->step_counter advanced by one between the calls (step t draws its device-generator disturbance from stream index
+ * (buf->step_counter + t) & 0x7FFFFFFF): state, derived (one sub-step stale), motor_thrust, actions / prev_actions, crashes and
+ * truncations (the last step's), sim_steps (+ steps), wrench_cmd where bound.  The state stays in registers in between.
+ *   actions            float [N][A] with actions_per_step == 0 (held for every step), [steps][N][A] with actions_per_step == 1
+ *   substeps           physics sub-steps of every step, 0 .. AGX_MAX_SUBSTEPS; with substeps_per_step: the LARGEST count in it
+ *                      (the launch sizes the sub-step positions in LDS by it; a larger entry is cut to it, a negative one to 0)
+ *   substeps_per_step  device int32 [steps], or NULL.  A count of 0: the step only counts (sim_steps + 1, crashes = 0)
+ *   record             NULL, or what to store after every step: channel c of step t goes to out[(t * channels + c) * N + env],
+ *                      component-major, a plain store nothing waits for.  source[c] / component[c] name the value:
+ *                        AGX_REC_STATE   0..12  position xyz, quaternion xyzw, linear velocity, angular velocity
+ *                        AGX_REC_DERIVED 0..15  Euler angles, vehicle-frame quaternion xyzw, vehicle-frame linear velocity,
+ *                                               body-frame linear velocity, body-frame angular velocity (buf->derived rows)
+ *                        AGX_REC_THRUST  0..M-1 motor thrusts
+ *                        AGX_REC_CRASH   0      this step's crash flag as 0.0f / 1.0f
+ *                      each (source, component) at most once, at most AGX_ROLLOUT_MAX_CHANNELS channels
+ *   first_crash_step   int32 [N] or NULL: the first step whose crash flag was set, or -1 (a crashed env keeps flying, as in
+ *                      the separate calls)
+ * Refused (AGX_E_ARG): AGX_CTRL_WRENCH, any launch_flags bit (split step, AGX_LAUNCH_LEAN, AGX_LAUNCH_ROV), buf->disturb,
+ * buf->body_force, buf->step_counter_dev, bound exchange rows / peer push; AGX_E_UNSUPPORTED: a motor count other than 4, 6, 8.
+ * No allocation, stream-ordered; one-wave workgroups up to 65536 envs, 256-thread workgroups above.                          */
+#define AGX_ROLLOUT_MAX_CHANNELS 32
+enum { AGX_REC_STATE = 0, AGX_REC_DERIVED = 1, AGX_REC_THRUST = 2, AGX_REC_CRASH = 3 };
+typedef struct AgxRolloutRecord {
+  float *out;                                   /* [steps][channels][N]                 */
+  int32_t channels;                             /* 1 .. AGX_ROLLOUT_MAX_CHANNELS        */
+  int32_t reserved;
+  int32_t source[AGX_ROLLOUT_MAX_CHANNELS];     /* AGX_REC_*                            */
+  int32_t component[AGX_ROLLOUT_MAX_CHANNELS];  /* row of that source                   */
+} AgxRolloutRecord;
+int agx_env_rollout(const AgxRobotParams *params, const AgxEnvBuffers *buf, int num_envs, const float *actions, int actions_per_step,
+                    int steps, int substeps, const int *substeps_per_step, const AgxRolloutRecord *record, int *first_crash_step,
+                    void *stream);
 
 /* EnvManager.compute_observations alone (env_manager.py:358-362; SURVEY 8b's minimum export set): crashes[i] |= the robot's
  * collision sphere (params->collision_radius) at its CURRENT position overlaps one of the env's obstacle boxes (buf->boxes,
