@@ -96,6 +96,45 @@ class DynHarness:
         _lib.check(self.lib.agx_dynamics_substeps(self.P, self.B, self.n, _lib.dptr(a), k, self.stream()), "dyn")
         torch.cuda.synchronize()
 
+    def rollout(self, actions, steps, substeps, per_step=None, record=None, first_crash=True, actions_per_step=None, guard=0,
+                sentinel=0, P=None):
+        """agx_env_rollout, called raw: -> (return code, record [T, C, N] or None, first_crash [N] or None).
+        actions: [N, A] (held) or [T, N, A], or None (a null pointer); actions_per_step: 0 / 1 by the shape unless given;
+        per_step: the int32 [T] sub-step counts, or None; record: a list of (source, component), an AgxRolloutRecord handed on as
+        it is, or None; first_crash: False hands a null pointer.  The record starts as NaN, first_crash as -7; `guard` elements
+        of `sentinel` lie behind each (kept in self.rollout_raw with the payload sizes).  The code is not checked: refusals are
+        what some callers are after."""
+        a = None if actions is None else torch.from_numpy(np.array(actions, np.float32)).to(self.dev)
+        if actions_per_step is None:
+            actions_per_step = 0 if (a is None or a.dim() == 2) else 1
+        ks = None if per_step is None else torch.from_numpy(np.array(per_step, np.int32)).to(self.dev)
+        self.rollout_raw = {}
+        rec, out = None, None
+        if isinstance(record, _lib.AgxRolloutRecord):
+            rec = record
+        elif record is not None:
+            rec = _lib.AgxRolloutRecord()
+            rec.channels = len(record)
+            for c, (src, comp) in enumerate(record):
+                rec.source[c], rec.component[c] = int(src), int(comp)
+            numel = max(steps, 0) * len(record) * self.n
+            raw = torch.full((numel + guard,), float("nan"), device=self.dev)
+            raw[numel:] = sentinel
+            out = raw[:numel].view(max(steps, 0), len(record), self.n)
+            rec.out = _lib.dptr(raw)
+            self.rollout_raw["record"] = (raw, numel)
+        first = None
+        if first_crash:
+            raw = torch.full((self.n + guard,), -7, dtype=torch.int32, device=self.dev)
+            raw[self.n:] = sentinel
+            first = raw[:self.n]
+            self.rollout_raw["first_crash"] = (raw, self.n)
+        rc = self.lib.agx_env_rollout(P or self.P, self.B, self.n, _lib.dptr(a), int(actions_per_step), int(steps), int(substeps),
+                                      _lib.dptr(ks), C.byref(rec) if rec is not None else None,
+                                      first.data_ptr() if first is not None else None, self.stream())
+        torch.cuda.synchronize()
+        return rc, (None if out is None else out.cpu().numpy()), (None if first is None else first.cpu().numpy())
+
     def robot_step(self, action, num_bodies, body_of_motor, substep=0):
         """agx_robot_step: BaseMultirotor.step as one launch -> (force [N, B, 3], torque [N, B, 3]) as the reference lays them out"""
         a = torch.from_numpy(np.ascontiguousarray(action, np.float32)).to(self.dev)
