@@ -315,6 +315,8 @@ class AgxVaeConv(C.Structure):
 
 
 VAE_ELU, VAE_LAYERS, MATH_EXPM1 = 1, 11, 5  # AGX_VAE_ELU, AGX_VAE_LAYERS, AGX_MATH_EXPM1
+VAE_FP32, VAE_BF16 = 0, 1  # AGX_VAE_FP32 / AGX_VAE_BF16: the encoder's precision
+VAE_OUT_F32, VAE_IN_IMAGE_F32 = 2, 4  # AGX_VAE_OUT_F32 / AGX_VAE_IN_IMAGE_F32: flags of the bf16 single-layer entries
 
 SNAPSHOT_MAX_ENTRIES = 96  # AGX_SNAPSHOT_MAX_ENTRIES
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 8, 512  # AGX_POLICY_MAX_LAYERS, AGX_POLICY_MAX_WIDTH
@@ -491,6 +493,14 @@ _SIGNATURES = {
     "agx_vae_envs_per_chunk": (C.c_int, [_P, C.c_size_t, C.c_int]),
     "agx_vae_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
     "agx_vae_layer_info": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    # its bf16 path (csrc/agx_vae_bf16.hip)
+    "agx_vae_packed_bf16_elems": (C.c_size_t, [C.POINTER(AgxVaeConv)]),
+    "agx_vae_pack_weight_bf16": (C.c_int, [C.POINTER(AgxVaeConv), _P, _P]),
+    "agx_vae_unpack_weight_bf16": (C.c_int, [C.POINTER(AgxVaeConv), _P, _P]),
+    "agx_vae_conv2d_bf16": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.POINTER(AgxVaeConv), C.c_int, _P, _P, _P]),
+    "agx_vae_linear_bf16": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "agx_vae_create_precision": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "agx_vae_precision": (C.c_int, [_P]),
     # snapshot / restore / fork of the simulator state (csrc/agx_snapshot.hip)
     "agx_state_gather": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P]),
     "agx_state_scatter": (C.c_int, [C.POINTER(AgxSnapshotTable), C.c_int, _P, _P, _P, _P]),

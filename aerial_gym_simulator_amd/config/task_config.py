@@ -140,6 +140,7 @@ class navigation_task_config:
         image_res = (270, 480)
         interpolation_mode = "nearest"
         return_sampled_latent = True
+        precision = "fp32"  # "bf16": bf16 activations and weights on the bf16 matrix instruction, fp32 accumulation (opt-in)
 
     class curriculum:
         min_level = 15

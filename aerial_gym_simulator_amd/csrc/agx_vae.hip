@@ -13,16 +13,15 @@
 #include "agx_device_math.h"
 #include "agx_rng.h"
 #include "agx_task_parts.h"
+#include "agx_vae.h"
 
 #include <vector>
 
 namespace {
 using namespace agx;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kLatent = 64;
-constexpr int kWavesPerBlock = 4;
+constexpr int kWavesPerBlock = kVaeWavesPerBlock;
 
 struct ConvK {
   const float *x, *w, *bias, *add;
@@ -98,7 +97,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_vae_conv(ConvK a) {
       const size_t idx = ((size_t)n * (size_t)a.cout + (size_t)co) * (size_t)ohw + (size_t)rem;
       float v = acc[t][i] + a.bias[co];
       if (a.add) v = v + a.add[idx];
-      if (a.elu) v = (v > 0.0f) ? v : expm1_cw(v);
+      if (a.elu) v = vae_elu(v);
       a.y[idx] = v;
     }
   }
@@ -142,8 +141,6 @@ __global__ void k_vae_place(int n, const float *__restrict__ latents, float *__r
   obs[(size_t)env * (size_t)obs_dim + (size_t)(obs_offset + (i - env * kLatent))] = latents[i];
 }
 
-inline int round_up8(int k) { return (k + 7) & ~7; }
-
 // ---- the encoder's layer table: Cin, Cout, kernel, stride, pad (h, w), the layer whose output it reads (-1: the image) ----
 struct LayerDef {
   int cin, cout, k, stride, pad_h, pad_w, input;
@@ -177,15 +174,15 @@ bool geometry(int image_h, int image_w, int hw[AGX_VAE_LAYERS][2]) {
   return hw[3][0] == hw[4][0] && hw[3][1] == hw[4][1] && hw[6][0] == hw[7][0] && hw[6][1] == hw[7][1] && hw[8][0] == 3 && hw[8][1] == 6;
 }
 
-size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 }  // namespace
 
 struct AgxVaeEncoder {
   int image_h, image_w;
+  int precision;  // AGX_VAE_FP32 / AGX_VAE_BF16
   int hw[AGX_VAE_LAYERS][2];
-  size_t out_floats[AGX_VAE_LAYERS];  // per env
-  float *w[AGX_VAE_LAYERS];           // device, packed
-  float *b[AGX_VAE_LAYERS];           // device
+  size_t out_bytes[AGX_VAE_LAYERS];  // per env: fp32, or bf16 for every layer but dense1
+  void *w[AGX_VAE_LAYERS];           // device, packed: float [K8][Cout], or bf16 [Cout][Kp]
+  float *b[AGX_VAE_LAYERS];          // device
 };
 
 extern "C" size_t agx_vae_packed_floats(int cout, int k) {
@@ -231,10 +228,7 @@ extern "C" int agx_vae_conv2d(int batch, const float *x, const float *w_packed, 
   a.pixels = (int)pixels;
   a.elu = (flags & AGX_VAE_ELU) ? 1 : 0;
   const int tiles = (a.pixels + 31) / 32;
-  // channel tiles per wave: 4 when that still leaves the device full of waves (the gathered tap is then used four times);
-  // the choice moves no result bit
-  int ct = 4;
-  while (ct > 1 && (a.cout % (32 * ct) != 0 || (long long)tiles * (a.cout / (32 * ct)) < 2048)) ct >>= 1;
+  const int ct = vae_channel_tiles(a.cout, tiles);
   const dim3 grid((unsigned)((tiles + kWavesPerBlock - 1) / kWavesPerBlock), (unsigned)(a.cout / (32 * ct))), block(64 * kWavesPerBlock);
   if (ct == 4) hipLaunchKernelGGL(k_vae_conv<4>, grid, block, 0, (hipStream_t)stream, a);
   else if (ct == 2) hipLaunchKernelGGL(k_vae_conv<2>, grid, block, 0, (hipStream_t)stream, a);
@@ -294,29 +288,61 @@ extern "C" int agx_vae_destroy(AgxVaeEncoder *enc) {
   return AGX_OK;
 }
 
+namespace {
+// the shape a layer's weights are packed under on the bf16 path: dense0 reads conv3_0's [3][6][128] output flattened
+AgxVaeConv pack_shape_bf16(int l) {
+  AgxVaeConv S = {};
+  S.cin = kLayers[l].cin; S.cout = kLayers[l].cout; S.kh = S.kw = kLayers[l].k;
+  if (l == 9) { S.cin = 128; S.kh = 3; S.kw = 6; }
+  return S;
+}
+}  // namespace
+
 extern "C" int agx_vae_create(const float *const *weights, const float *const *biases, int image_h, int image_w, int latent_dims,
                               AgxVaeEncoder **out) {
+  return agx_vae_create_precision(weights, biases, image_h, image_w, latent_dims, AGX_VAE_FP32, out);
+}
+
+extern "C" int agx_vae_precision(const AgxVaeEncoder *enc) { return enc ? enc->precision : -1; }
+
+extern "C" int agx_vae_create_precision(const float *const *weights, const float *const *biases, int image_h, int image_w, int latent_dims,
+                                        int precision, AgxVaeEncoder **out) {
   AGX_REQUIRE(weights && biases && out, "agx_vae_create: null argument");
   *out = nullptr;
+  AGX_REQUIRE(precision == AGX_VAE_FP32 || precision == AGX_VAE_BF16, "agx_vae_create_precision: precision = %d (AGX_VAE_FP32 or AGX_VAE_BF16)",
+              precision);
+  const bool bf16 = precision == AGX_VAE_BF16;
   AGX_REQUIRE(latent_dims == kLatent, "agx_vae_create: latent_dims = %d; this encoder (dense1: 512 -> 128) has 64", latent_dims);
   int32_t flat[2 * AGX_VAE_LAYERS];
   if (int e = agx_vae_geometry(image_h, image_w, flat)) return e;
   for (int l = 0; l < AGX_VAE_LAYERS; ++l) AGX_REQUIRE(weights[l] && biases[l], "agx_vae_create: layer %d: null weight or bias", l);
   AgxVaeEncoder *enc = new AgxVaeEncoder();
   enc->image_h = image_h; enc->image_w = image_w;
+  enc->precision = precision;
   for (int l = 0; l < AGX_VAE_LAYERS; ++l) {
     enc->hw[l][0] = flat[2 * l]; enc->hw[l][1] = flat[2 * l + 1];
-    enc->out_floats[l] = (size_t)kLayers[l].cout * (size_t)enc->hw[l][0] * (size_t)enc->hw[l][1];
-    enc->w[l] = enc->b[l] = nullptr;
+    enc->out_bytes[l] = (size_t)kLayers[l].cout * (size_t)enc->hw[l][0] * (size_t)enc->hw[l][1] * (bf16 && l != 10 ? sizeof(uint16_t) : sizeof(float));
+    enc->w[l] = nullptr;
+    enc->b[l] = nullptr;
   }
   for (int l = 0; l < AGX_VAE_LAYERS; ++l) {
     const LayerDef &L = kLayers[l];
     const int k = L.cin * L.k * L.k;
-    std::vector<float> packed(agx_vae_packed_floats(L.cout, k));
-    agx_vae_pack_weight(L.cout, k, weights[l], packed.data());
-    hipError_t e = hipMalloc((void **)&enc->w[l], packed.size() * sizeof(float));
+    std::vector<float> packed;
+    std::vector<uint16_t> packed16;
+    if (bf16) {
+      const AgxVaeConv S = pack_shape_bf16(l);
+      packed16.resize(agx_vae_packed_bf16_elems(&S));
+      agx_vae_pack_weight_bf16(&S, weights[l], packed16.data());
+    } else {
+      packed.resize(agx_vae_packed_floats(L.cout, k));
+      agx_vae_pack_weight(L.cout, k, weights[l], packed.data());
+    }
+    const void *src = bf16 ? (const void *)packed16.data() : (const void *)packed.data();
+    const size_t bytes = bf16 ? packed16.size() * sizeof(uint16_t) : packed.size() * sizeof(float);
+    hipError_t e = hipMalloc(&enc->w[l], bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&enc->b[l], (size_t)L.cout * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(enc->w[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(enc->w[l], src, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(enc->b[l], biases[l], (size_t)L.cout * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       agx_vae_destroy(enc);
@@ -333,7 +359,7 @@ namespace {
 // chunk: a workspace of agx_vae_workspace_bytes(n) bytes runs exactly n envs per chunk.
 size_t ws_offset(const AgxVaeEncoder *enc, int chunk, int l) {
   size_t off = 0;
-  for (int j = 0; j < l; ++j) off += (size_t)chunk * align256(enc->out_floats[j] * sizeof(float));
+  for (int j = 0; j < l; ++j) off += (size_t)chunk * align256(enc->out_bytes[j]);
   return off;
 }
 constexpr int kMaxChunk = 65536;
@@ -354,11 +380,54 @@ extern "C" size_t agx_vae_workspace_bytes(const AgxVaeEncoder *enc, int envs_per
 extern "C" int agx_vae_layer_info(const AgxVaeEncoder *enc, int layer, int envs_per_chunk, const float **w_packed, const float **bias,
                                   size_t *out_offset_bytes) {
   AGX_REQUIRE(enc && layer >= 0 && layer < AGX_VAE_LAYERS && envs_per_chunk > 0 && envs_per_chunk <= 65536, "agx_vae_layer_info: bad arguments");
-  if (w_packed) *w_packed = enc->w[layer];
+  if (w_packed) *w_packed = (const float *)enc->w[layer];
   if (bias) *bias = enc->b[layer];
   if (out_offset_bytes) *out_offset_bytes = ws_offset(enc, envs_per_chunk, layer);
   return AGX_OK;
 }
+
+namespace {
+// agx_vae_encode on a bf16 handle: the same chunks and the same layer order, every layer one public bf16 call
+int encode_bf16(AgxVaeEncoder *enc, int chunk, int num_envs, const float *pixels, int src_h, int src_w, const int32_t *row_map,
+                const int32_t *col_map, const float *eps, float *latents, float *means, float *stdv, void *workspace, uint64_t rng_seed,
+                int env_index_base, int env_step, void *stream) {
+  void *out[AGX_VAE_LAYERS];
+  for (int l = 0; l < AGX_VAE_LAYERS; ++l) out[l] = (char *)workspace + ws_offset(enc, chunk, l);
+  for (int e0 = 0; e0 < num_envs; e0 += chunk) {
+    const int c = num_envs - e0 < chunk ? num_envs - e0 : chunk;
+    for (int o = 0; o < AGX_VAE_LAYERS; ++o) {
+      const int l = kOrder[o];
+      const LayerDef &L = kLayers[l];
+      const void *x = L.input < 0 ? (const void *)(pixels + (size_t)e0 * (size_t)src_h * (size_t)src_w) : out[L.input];
+      int flags = (l == 1 || l == 3 || l == 6 || l == 9) ? AGX_VAE_ELU : 0;
+      const uint16_t *w = (const uint16_t *)enc->w[l];
+      int e;
+      if (l >= kConvLayers) {
+        if (l == 10) flags |= AGX_VAE_OUT_F32;
+        e = agx_vae_linear_bf16(c, (const uint16_t *)x, w, enc->b[l], out[l], L.cin, L.cout, flags, stream);
+      } else {
+        AgxVaeConv S;
+        S.cin = L.cin; S.cout = L.cout; S.kh = S.kw = L.k; S.stride = L.stride; S.pad_h = L.pad_h; S.pad_w = L.pad_w;
+        S.in_h = L.input < 0 ? enc->image_h : enc->hw[L.input][0];
+        S.in_w = L.input < 0 ? enc->image_w : enc->hw[L.input][1];
+        S.out_h = enc->hw[l][0]; S.out_w = enc->hw[l][1];
+        S.src_h = L.input < 0 ? src_h : S.in_h;
+        S.src_w = L.input < 0 ? src_w : S.in_w;
+        if (L.input < 0) flags |= AGX_VAE_IN_IMAGE_F32;
+        const uint16_t *add = (const uint16_t *)(l == 3 ? out[4] : (l == 6 ? out[7] : nullptr));
+        e = agx_vae_conv2d_bf16(c, x, w, enc->b[l], add, out[l], &S, flags, L.input < 0 ? row_map : nullptr, L.input < 0 ? col_map : nullptr,
+                                stream);
+      }
+      if (e) return e;
+    }
+    const size_t at = (size_t)e0 * kLatent;
+    if (int e = agx_vae_sample(c, (const float *)out[10], eps ? eps + at : nullptr, latents + at, means ? means + at : nullptr,
+                               stdv ? stdv + at : nullptr, rng_seed, env_index_base + e0, env_step, stream))
+      return e;
+  }
+  return AGX_OK;
+}
+}  // namespace
 
 extern "C" int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pixels, int src_h, int src_w, const int32_t *row_map,
                               const int32_t *col_map, const float *eps, float *latents, float *means, float *stdv, void *workspace,
@@ -371,6 +440,9 @@ extern "C" int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pix
               src_h, src_w, enc->image_h, enc->image_w);
   const int chunk = agx_vae_envs_per_chunk(enc, workspace_bytes, num_envs);  // the largest the workspace holds
   AGX_REQUIRE(chunk >= 1, "agx_vae_encode: workspace of %zu bytes, one env needs %zu", workspace_bytes, ws_offset(enc, 1, AGX_VAE_LAYERS));
+  if (enc->precision == AGX_VAE_BF16)
+    return encode_bf16(enc, chunk, num_envs, pixels, src_h, src_w, row_map, col_map, eps, latents, means, stdv, workspace, rng_seed, env_index_base,
+                       env_step, stream);
   float *out[AGX_VAE_LAYERS];
   for (int l = 0; l < AGX_VAE_LAYERS; ++l) out[l] = (float *)((char *)workspace + ws_offset(enc, chunk, l));
   for (int e0 = 0; e0 < num_envs; e0 += chunk) {
@@ -382,7 +454,7 @@ extern "C" int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pix
       const int flags = (l == 1 || l == 3 || l == 6 || l == 9) ? AGX_VAE_ELU : 0;
       int e;
       if (l >= kConvLayers) {
-        e = agx_vae_linear(c, x, enc->w[l], enc->b[l], out[l], L.cin, L.cout, flags, stream);
+        e = agx_vae_linear(c, x, (const float *)enc->w[l], enc->b[l], out[l], L.cin, L.cout, flags, stream);
       } else {
         AgxVaeConv S;
         S.cin = L.cin; S.cout = L.cout; S.kh = S.kw = L.k; S.stride = L.stride; S.pad_h = L.pad_h; S.pad_w = L.pad_w;
@@ -392,7 +464,7 @@ extern "C" int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pix
         S.src_h = L.input < 0 ? src_h : S.in_h;
         S.src_w = L.input < 0 ? src_w : S.in_w;
         const float *add = l == 3 ? out[4] : (l == 6 ? out[7] : nullptr);
-        e = agx_vae_conv2d(c, x, enc->w[l], enc->b[l], add, out[l], &S, flags, L.input < 0 ? row_map : nullptr,
+        e = agx_vae_conv2d(c, x, (const float *)enc->w[l], enc->b[l], add, out[l], &S, flags, L.input < 0 ? row_map : nullptr,
                            L.input < 0 ? col_map : nullptr, stream);
       }
       if (e) return e;

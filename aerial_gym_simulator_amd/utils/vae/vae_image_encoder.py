@@ -111,6 +111,37 @@ def unpack_weight(packed, shape):
     return w
 
 
+def _bf16_shape(shape):
+    """the AgxVaeConv the bf16 pack reads: [Cout, Cin, kh, kw], a dense [out, in] as a 1 x 1 kernel"""
+    shape = tuple(int(v) for v in shape)
+    cout, cin, kh, kw = shape if len(shape) == 4 else (shape[0], shape[1], 1, 1)
+    return _lib.AgxVaeConv(cin=cin, cout=cout, kh=kh, kw=kw)
+
+
+def pack_weight_bf16(w):
+    """torch layout [Cout, Cin, kh, kw] (or [out, in]) -> the bf16 kernels' [Cout][Kp], k = (kh, kw, ci), rounded to nearest even,
+    Kp = K rounded up to 16 with a zero tail (uint16 numpy, host).  A dense layer that reads a flattened [H, W, C] activation
+    is packed from its weight viewed as [out, C, H, W] (dense0: `w.reshape(512, 128, 3, 6)`)."""
+    w = np.ascontiguousarray(np.asarray(w, np.float32))
+    S, lib = _bf16_shape(w.shape), _lib.load()
+    packed = np.empty(lib.agx_vae_packed_bf16_elems(C.byref(S)), np.uint16)
+    _lib.check(lib.agx_vae_pack_weight_bf16(C.byref(S), w.ctypes.data, packed.ctypes.data), "agx_vae_pack_weight_bf16")
+    return packed
+
+
+def unpack_weight_bf16(packed, shape):
+    """the rounded values of a pack_weight_bf16 result, float32 in torch's layout `shape`"""
+    S, lib = _bf16_shape(shape), _lib.load()
+    packed = np.ascontiguousarray(packed, np.uint16)
+    assert packed.size == lib.agx_vae_packed_bf16_elems(C.byref(S)), (packed.size, shape)
+    w = np.empty(tuple(int(v) for v in shape), np.float32)
+    _lib.check(lib.agx_vae_unpack_weight_bf16(C.byref(S), packed.ctypes.data, w.ctypes.data), "agx_vae_unpack_weight_bf16")
+    return w
+
+
+PRECISIONS = {"fp32": _lib.VAE_FP32, "bf16": _lib.VAE_BF16}
+
+
 class VAEImageEncoder(torch.nn.Module):
     DEFAULT_WORKSPACE_MB = 1024
 
@@ -118,6 +149,9 @@ class VAEImageEncoder(torch.nn.Module):
         super().__init__()
         self.config = config
         self.device = device
+        self.precision = getattr(config, "precision", "fp32")
+        if self.precision not in PRECISIONS:
+            raise ValueError(f"vae_config.precision = {self.precision!r}: this encoder runs in 'fp32' or 'bf16'")
         if int(config.latent_dims) != LATENT_DIMS:
             raise ValueError(f"vae_config.latent_dims = {config.latent_dims}: this encoder has {LATENT_DIMS} latents")
         self.image_res = (int(config.image_res[0]), int(config.image_res[1]))
@@ -129,7 +163,8 @@ class VAEImageEncoder(torch.nn.Module):
         bp = (C.c_void_p * _lib.VAE_LAYERS)(*[b.data_ptr() for b in biases])
         handle = C.c_void_p()
         with torch.cuda.device(torch.device(device)):
-            _lib.check(self._lib.agx_vae_create(wp, bp, self.image_res[0], self.image_res[1], LATENT_DIMS, C.byref(handle)), "agx_vae_create")
+            _lib.check(self._lib.agx_vae_create_precision(wp, bp, self.image_res[0], self.image_res[1], LATENT_DIMS,
+                                                          PRECISIONS[self.precision], C.byref(handle)), "agx_vae_create_precision")
         self._handle = handle
         self.workspace_bytes_budget = int(workspace_mb if workspace_mb is not None else self.DEFAULT_WORKSPACE_MB) << 20
         self.rng_seed, self.env_index_base, self.env_step = int(rng_seed), 0, 0

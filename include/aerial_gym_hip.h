@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define AGX_ABI_VERSION 25  /* (agx_env_rollout / AgxRolloutRecord were ADDED under 25: a new symbol and a new struct, no existing
-                               layout or signature changed, so a caller built against the earlier 25 header keeps working) */
+                               layout or signature changed, so a caller built against the earlier 25 header keeps working;
+                               likewise the bf16 entries of the VAE encoder: new symbols and enums only) */
 #define AGX_MAX_MOTORS 8
 #define AGX_MAX_ACTIONS 8
 #define AGX_MAX_SUBSTEPS 32
@@ -1183,9 +1184,47 @@ int agx_vae_encode(AgxVaeEncoder *enc, int num_envs, const float *pixels, int sr
                    const int32_t *col_map, const float *eps, float *latents, float *means, float *std, void *workspace,
                    size_t workspace_bytes, uint64_t rng_seed, int env_index_base, int env_step, void *stream);
 /* Diagnostic: the device copies of layer `layer` (packed weights, bias) and the buffer of its output inside a workspace
- * laid out for `envs_per_chunk` envs (byte offset).                                                                       */
+ * laid out for `envs_per_chunk` envs (byte offset).  On a bf16 handle *w_packed is the bf16 copy ([Cout][Kp] uint16_t behind
+ * the float pointer) and the offsets are those of the bf16 workspace; the bias is fp32 in both.                           */
 int agx_vae_layer_info(const AgxVaeEncoder *enc, int layer, int envs_per_chunk, const float **w_packed, const float **bias,
                        size_t *out_offset_bytes);
+
+/* ---- the bf16 path of the encoder (csrc/agx_vae_bf16.hip), opt-in; everything above is unchanged by it -------------------
+ * Arithmetic: weights rounded ONCE to bf16 (nearest even) when packed, the depth image rounded to bf16 as conv0 reads it,
+ * biases fp32.  Products are exact and accumulate in fp32 inside v_mfma_f32_32x32x16_bf16, all of K in one chain per output
+ * element (no split-K) in the k order of the packing: the result of an element does not depend on batch size, env index,
+ * tile, channel-tile count or chunking (the order INSIDE one instruction is the hardware's).  Epilogue in fp32: + bias, then
+ * (optionally) + the second tensor (stored bf16, widened), then (optionally) ELU (expm1_cw), then ONE round to nearest even
+ * for the bf16 store.
+ * Layout: activations [B][H][W][C] bf16; weights [Cout][Kp] bf16 with k = (kh, kw, ci), ci fastest, Kp = K rounded up to 16,
+ * the tail zero.  A dense layer that reads a flattened [H][W][C] activation is packed with the AgxVaeConv of that
+ * activation (cin = C, kh = H, kw = W): its torch columns (c, h, w) land in (h, w, c) order.
+ * A tap outside the image and a pixel past the batch are never addressed.                                                  */
+enum { AGX_VAE_FP32 = 0, AGX_VAE_BF16 = 1 };           /* encoder precision */
+enum { AGX_VAE_OUT_F32 = 2, AGX_VAE_IN_IMAGE_F32 = 4 }; /* flags of the bf16 entries, beside AGX_VAE_ELU: y is fp32 [B][H][W][C];
+                                                           x is the fp32 planar image [B][src_h][src_w] (cin == 1 only) */
+/* Host functions on host memory; only cin, cout, kh, kw of `shape` are read.  w / the unpacked result: torch's
+ * [cout][cin][kh][kw] fp32 (unpack returns the ROUNDED values); packed: agx_vae_packed_bf16_elems(shape) uint16_t.       */
+size_t agx_vae_packed_bf16_elems(const AgxVaeConv *shape);
+int agx_vae_pack_weight_bf16(const AgxVaeConv *shape, const float *w, uint16_t *packed);
+int agx_vae_unpack_weight_bf16(const AgxVaeConv *shape, const uint16_t *packed, float *w);
+/* y [B][out_h][out_w][cout] (bf16, or fp32 with AGX_VAE_OUT_F32) <- conv(x [B][src_h][src_w][cin] bf16) + bias [cout] fp32
+ * (+ add, bf16 [B][out_h][out_w][cout]) (ELU).  With AGX_VAE_IN_IMAGE_F32 x is the fp32 image and row_map / col_map act as
+ * in agx_vae_conv2d.  AGX_E_ARG before any device call: a null buffer, cout % 32, cin % 8 without the image flag, the image
+ * flag with cin != 1, index tables without the image flag, x / w_packed / add / y not 16-byte aligned, unknown flag bits.  */
+int agx_vae_conv2d_bf16(int batch, const void *x, const uint16_t *w_packed, const float *bias, const uint16_t *add, void *y,
+                        const AgxVaeConv *shape, int flags, const int32_t *row_map, const int32_t *col_map, void *stream);
+/* y [B][out_features] <- x [B][in_features] (bf16) W^T + bias (ELU): the same kernel at 1 x 1 spatial size
+ * (in_features % 8 == 0, out_features % 32 == 0; flags: AGX_VAE_ELU, AGX_VAE_OUT_F32).                                     */
+int agx_vae_linear_bf16(int batch, const uint16_t *x, const uint16_t *w_packed, const float *bias, void *y, int in_features,
+                        int out_features, int flags, void *stream);
+/* agx_vae_create with a precision (AGX_VAE_FP32: exactly agx_vae_create).  On a AGX_VAE_BF16 handle agx_vae_workspace_bytes,
+ * agx_vae_envs_per_chunk and agx_vae_encode follow the precision: every layer's buffer is bf16 but dense1's (fp32, what
+ * agx_vae_sample reads), the workspace is still linear in the chunk, and agx_vae_encode issues exactly the single-layer
+ * bf16 calls above (conv0 with AGX_VAE_IN_IMAGE_F32, dense1 with AGX_VAE_OUT_F32).                                         */
+int agx_vae_create_precision(const float *const *weights, const float *const *biases, int image_h, int image_w,
+                             int latent_dims, int precision, AgxVaeEncoder **out);
+int agx_vae_precision(const AgxVaeEncoder *enc);       /* AGX_VAE_FP32 / AGX_VAE_BF16; -1 for NULL */
 
 /* ---- snapshot / restore / fork of the simulator state (csrc/agx_snapshot.hip) ---------------------------------------------
  * The state of a running simulation is spread over many tensors (AgxEnvBuffers, obstacle poses, sensor images and mounts,
